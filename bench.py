@@ -16,10 +16,19 @@ search and the first transitions are behind every chain).
 Prints ONE JSON line (rank 0).  `value` = gradient evaluations actually executed by all ranks during the timed
 region (device counter) / wall time (max over ranks).  `roofline` is for the dominant kernel (nuts_kernel):
 achieved = algorithmic FLOPs per launch (4.27e5 per evaluation) / HIP-event launch duration on the
-sampler's stream.  `cpu_baseline` = the CPU oracle (plain C port of the same log-posterior+gradient, -O3 -march=native)
-inside the oracle's NUTS driver, timed on this box's host cores: one core, and one chain per core on all cores.
-N > 1 additionally times, outside the steady-state region, one complete `parallel.sample_sharded` call (broadcast of
-the problem + short run + gather of per-spectrum summaries over RCCL) and reports it in `config.dist_roundtrip`.
+sampler's stream.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds the figures that
+take runs of their own, all outside the timed region: `cpu_baseline` = the CPU oracle (plain C port of the same
+log-posterior+gradient, -O3 -march=native) inside the oracle's NUTS driver, timed on this box's host cores: one core, and one
+chain per core on all cores; the mid-occupancy, per-shape, raw-kernel and config-3 tables; for N > 1 config 4 as written
+(`config.strong_scaling`) and one complete `parallel.sample_sharded` call (broadcast of the problem + short run + gather of
+per-spectrum summaries over RCCL), reported in `config.dist_roundtrip`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the sampler returns to its caller (`Sampler.results()`: the chains are
+in warm-up for the whole run, so no draw exists yet and the outputs are the per-chain step size, mean acceptance and leapfrog /
+divergence / tree-depth counts of rank 0's units) as DIR/<name>.npy in float64.  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -328,6 +337,26 @@ def shape_problem_kwargs(nf, k, n_spectra, seed=7):
     return dict(blocks=[blk], Z=Z, freq=f, sigma_min=0.002, ups_alpha=1.0, ups_beta=0.1, induc_scale=1.0)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """arrays: name -> array with one row per unit.  Writes DIR/<name>.npy in float64.  If they would take more than `limit`
+    bytes together, every array is cut to the same fixed, seeded sample of units, whose indices go to DIR/units.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = min(len(v) for v in arrays.values())
+    per_unit = sum(v[0].nbytes for v in arrays.values()) if n else 0
+    budget = limit - 4096 * (len(arrays) + 1)                     # room for the .npy headers
+    if per_unit * n > budget:
+        keep = max(1, budget // (per_unit + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays['units'] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+
+
 def steady_rate(prob, n_units, ctrl, n_spectra, rounds=500, launches=4, warm_rounds=600):
     """evals/s of n_units real NUTS chains in their warm-up (no chain finishes), after warm_rounds untimed rounds: the short form
     of the headline measurement, for the tables that accompany it (outside the timed region)."""
@@ -354,10 +383,15 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=8.0)
     ap.add_argument('--phase-profile', action='store_true', help='print the in-kernel cycle breakdown (perturbs timing)')
+    ap.add_argument('--full', action='store_true', help='also the CPU baseline, the tables beside the headline and, for N > 1, '
+                                                        'strong scaling and the sharded round trip (each outside the timed region)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the sampler returns after the last timed step as DIR/<name>.npy')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if args.gpus > 1 and 'RANK' not in os.environ:
         # started bare: become the launcher.  Nothing in this process has touched the GPU yet (device_count() does not
         # initialise HIP on this image), and the ranks are a CHILD process, never an exec.
@@ -373,7 +407,7 @@ def main():
 
     # CPU baseline first (rank 0, N=1 only), before this process touches the GPU: workers are plain subprocesses
     cpu = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
 
     import torch
@@ -485,13 +519,19 @@ def main():
         for k, nm in enumerate(['entry -> B1 (P1, prior chain)', 'B1 -> B2 (forward GEMM)', 'B2 -> B3 (likelihood)']):
             print('WAVE-AVG tile %-30s %6.0f cycles/round' % (nm, cyc[29 + k] / n_wg / rounds_total / 8), file=sys.stderr)
         print('half-waves per round in stage E (new start point): %.2f of 16' % (cyc[24] / n_wg / rounds_total * 2), file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        # every chain is still in warm-up (no draw yet: draws and lp hold nothing the run computed), so what the caller receives
+        # is the per-chain state of the adaptation
+        _, _, diag = smp.results(want_draws=False)
+        write_outputs(args.dump_outputs, {k: [d[k] for d in diag] for k in
+                                          ('stepsize', 'mean_accept', 'n_leapfrog', 'n_divergent', 'n_max_treedepth')})
     smp.close()
 
     # ---- strong scaling: BASELINE config 4 AS WRITTEN -- 512 spectra x 8 chains in total, 512 / N spectra per rank -- timed the
     # same way (barrier + synchronize on both sides, max over ranks), beside the weak-scaling value above.  At N = 1 it is the
     # same job as the headline and is not run twice.
     strong = None
-    if world > 1:
+    if args.full and world > 1:
         ns_total = min(N_SPECTRA, n_global)               # (a test run with fewer spectra than config 4 has: all of them)
         su0, su1 = par.partition_units(ns_total, args.chains, world)[rank]
         sspec, schain = par.make_units(ns_total, args.chains)
@@ -532,7 +572,7 @@ def main():
     # ---- fewer chains than the tiles want (the regime of 8-GPU runs of config 4, of config 3 x many spectra, of a run's tail) and
     # the other shapes of the reference's fits: steady-state rates of the same kind, outside the timed region (rank 0, N = 1)
     mid, shapes = None, None
-    if rank == 0 and args.gpus == 1 and not os.environ.get('BDRT_BENCH_NO_TABLES'):
+    if args.full and rank == 0 and args.gpus == 1 and not os.environ.get('BDRT_BENCH_NO_TABLES'):
         mid = []
         for nu in (512, 1024, 2048):
             r, kind = steady_rate(prob, nu, ctrl, prob.n_spectra)
@@ -554,7 +594,7 @@ def main():
 
     # ---- raw log-posterior+gradient kernel at B = 1 .. 4096 points, inputs resident in HBM; outside the timed region
     sweep = None
-    if rank == 0 and args.gpus == 1:
+    if args.full and rank == 0 and args.gpus == 1:
         sweep = []
         ts = torch.cuda.Stream()
         for B in (1, 4, 32, 512, 4096):
@@ -577,7 +617,7 @@ def main():
     # ---- BASELINE config 3 (the reference's own call shape: 4 chains of one spectrum): latency-bound, reported beside the
     # throughput figure as SURVEY 8(d) asks.  One-chain-per-workgroup kernel (bdrt_solo.h); outside the timed region.
     few = None
-    if rank == 0 and args.gpus == 1:
+    if args.full and rank == 0 and args.gpus == 1:
         p1 = Problem(blocks, np.atleast_2d(Zall)[:1], freq, **local_kw)
         s4 = Sampler(p1, 4, 1000000, 1, 1234, ctrl)
         s4.advance(2000); s4.sync()
@@ -700,9 +740,9 @@ def main():
     else:
         line = None
 
-    # ---- N > 1: one complete sample_sharded call (broadcast of the problem + short run + summary gather over RCCL), timed
-    # apart from the rate and AFTER it has been secured: a watchdog prints the line and ends the process should the exercise
-    # (or the teardown of the process group) not come back -- the steady-state measurement must not hang on it
+    # ---- N > 1 with --full: one complete sample_sharded call (broadcast of the problem + short run + summary gather over RCCL),
+    # timed apart from the rate and AFTER it has been secured: a watchdog prints the line and ends the process should the exercise
+    # (or, with or without --full, the teardown of the process group) not come back -- the steady-state measurement must not hang on it
     printed = threading.Event()
     finished = threading.Event()
     emit_lock = threading.Lock()
@@ -724,6 +764,7 @@ def main():
                 # exercise), the exit code says the round trip failed (WATCHDOG_EXIT; self_launch relays both)
                 os._exit(WATCHDOG_EXIT)
         threading.Thread(target=watchdog, daemon=True).start()
+    if use_dist and args.full:
         small = dict(kw, Z=np.atleast_2d(Zall)[:8 * world]) if rank == 0 else None
         t_rt = time.perf_counter()
         try:

@@ -38,6 +38,7 @@ def main():
         res = par.sample_sharded(pk, 5, 2, 8, 6, seed=99, control={'max_treedepth': 5}, gather='draws')
         summ = par.sample_sharded(pk, 5, 2, 8, 6, seed=99, control={'max_treedepth': 5}, gather='summary')
         one = par.sample_sharded(None if rank else dict(pk, Z=pk['Z'][:1]), 1, 4, 8, 6, seed=99, control={'max_treedepth': 5}, gather='draws')
+        three = par.sample_sharded(None if rank else dict(pk, Z=pk['Z'][:1]), 1, 3, 8, 6, seed=99, control={'max_treedepth': 5}, gather='draws')
         f, zs = _spectra(3)
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
@@ -45,7 +46,7 @@ def main():
             vm = Inverter(basis_freq=f).fit_many(f, zs, nonneg=True, mode='optimize')
         if rank == 0:
             np.savez(out_path, ranks_seen=int(ones.item()), device_ids=np.array(ids), draws=res['draws'], lp=res['lp'], stats=res['stats'],
-                     mean=res['mean'], pct=res['pct'], s_mean=summ['mean'], s_pct=summ['pct'], one_draws=one['draws'],
+                     mean=res['mean'], pct=res['pct'], s_mean=summ['mean'], s_pct=summ['pct'], one_draws=one['draws'], three_draws=three['draws'],
                      fit_theta=np.stack([v._sample_result.theta for v in vs]), fit_coef=np.stack([v.distribution_fits['DRT']['coef'] for v in vm]))
     finally:
         dist.destroy_process_group()

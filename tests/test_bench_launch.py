@@ -55,3 +55,26 @@ def test_physical_core_count():
     import bench
     n = bench.physical_cores()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+def test_dump_outputs_stay_within_their_budget(tmp_path):
+    """--dump-outputs: arrays that fit are written whole in float64; arrays over the budget are cut to one fixed, seeded sample
+    of units (the same rows for every array, their indices in units.npy)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rs = np.random.default_rng(1)
+    arrays = {'draws': rs.normal(size=(600, 1, 331)), 'lp': rs.normal(size=(600, 1)), 'n_leapfrog': np.arange(600)}
+    bench.write_outputs(str(tmp_path / 'whole'), arrays)
+    whole = {k: np.load(str(tmp_path / 'whole' / (k + '.npy'))) for k in arrays}
+    assert not os.path.exists(str(tmp_path / 'whole' / 'units.npy'))
+    assert all(whole[k].dtype == np.float64 and np.array_equal(whole[k], arrays[k]) for k in arrays)
+    limit = 1 << 20
+    for run in ('a', 'b'):
+        bench.write_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert sum(os.path.getsize(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))) <= limit
+    rows = np.load(str(tmp_path / 'a' / 'units.npy'))
+    assert np.array_equal(rows, np.load(str(tmp_path / 'b' / 'units.npy'))) and 0 < len(rows) < 600
+    idx = rows.astype(int)
+    for k in arrays:
+        assert np.array_equal(np.load(str(tmp_path / 'a' / (k + '.npy'))), arrays[k][idx].astype(np.float64))

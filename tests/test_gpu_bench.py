@@ -1,7 +1,8 @@
 """GPU tests (-m gpu) of bench.py.
-(1) The driver's exact single-GPU command line (`bench.py --gpus 1 --steps 20 --warmup 5`): the timed region must be the
-    steady state -- at least 0.3 s of sampling, every unit evaluated once per round -- and the line must carry `roofline`
-    and `cpu_baseline` (with the single-core figure and the labelled pystan estimate).
+(1) The driver's single-GPU command line with `--full` (`bench.py --gpus 1 --steps 20 --warmup 5 --full`): the timed region must
+    be the steady state -- at least 0.3 s of sampling, every unit evaluated once per round -- and the line must carry `roofline`
+    and `cpu_baseline` (with the single-core figure and the labelled pystan estimate).  Without `--full` the line holds the
+    headline alone, and `--dump-outputs` writes what the sampler returned, the same from run to run.
 (2) bench.py under the launcher the driver uses for N > 1 (`python -m torch.distributed.run`), with one rank and
     BDRT_BENCH_FORCE_DIST=1 so that the RCCL code path (init_process_group, problem broadcast, barrier, all_reduce of the
     timing / evaluation counts, the sample_sharded round trip, destroy) runs on a 1-GPU box."""
@@ -29,7 +30,7 @@ def _line(out):
 
 
 def test_driver_command_line_times_the_steady_state():
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--cpu-seconds', '2']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--cpu-seconds', '2', '--full']
     d = _line(subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900))
     c, r = d['config'], d['roofline']
     assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['scaling'] == 'weak' and d['dtype'] == 'f64'
@@ -67,11 +68,40 @@ def test_driver_command_line_times_the_steady_state():
     assert b['pystan_derived']['value'] > 0 and 'derived' in b['pystan_derived']['source']
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries no figure measured outside the timed region; --dump-outputs writes what the sampler
+    returned after the last timed step (the per-chain diagnostics of chains in warm-up), in float64, and two runs with the same
+    arguments write the same arrays."""
+    import numpy as np
+    outs = []
+    for run in range(2):
+        d_out = tmp_path / ('run%d' % run)
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--rounds', '50',
+               '--spectra', '32', '--dump-outputs', str(d_out)]
+        d = _line(subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600))
+        c = d['config']
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'evals/s' and d['higher_is_better'] is True
+        assert c['evals_in_timed_region'] == c['units_per_gpu'] * 50 * 3
+        assert abs(d['ms_per_step'] * 3 - c['timed_region_s'] * 1e3) < 1e-6 * c['timed_region_s'] * 1e3
+        assert 'cpu_baseline' not in d
+        for k in ('few_chains', 'mid_occupancy', 'shapes', 'raw_logp_grad_kernel_sweep', 'dist_roundtrip'):
+            assert k not in c, k
+        names = sorted(f for f in os.listdir(d_out))
+        assert names == sorted(k + '.npy' for k in ('stepsize', 'mean_accept', 'n_leapfrog', 'n_divergent', 'n_max_treedepth'))
+        arrs = {f[:-4]: np.load(os.path.join(d_out, f)) for f in names}
+        assert all(a.dtype == np.float64 and a.shape == (c['units_per_gpu'],) for a in arrs.values())
+        assert np.all(arrs['stepsize'] > 0) and np.all(arrs['n_leapfrog'] > 0)
+        assert sum(os.path.getsize(os.path.join(d_out, f)) for f in names) <= 64 << 20
+        outs.append(arrs)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], outs[1][k]), k
+
+
 def test_bench_contract_under_torchrun_single_rank():
     env = dict(os.environ, BDRT_BENCH_FORCE_DIST='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4',
-           '--warmup', '2', '--rounds', '50', '--no-cpu-baseline', '--spectra', '64']
+           '--warmup', '2', '--rounds', '50', '--no-cpu-baseline', '--spectra', '64', '--full']
     d = _line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600))
     assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['scaling'] == 'weak' and d['dtype'] == 'f64'
     assert d['value'] > 1e6 and d['unit'] == 'evals/s' and 'workload' in d['config']
@@ -89,7 +119,7 @@ def test_bench_two_ranks_on_the_one_device():
     env = dict(os.environ, BDRT_BENCH_ONE_DEVICE='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', '29541', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3',
-           '--warmup', '1', '--rounds', '40', '--no-cpu-baseline', '--spectra', '32']
+           '--warmup', '1', '--rounds', '40', '--no-cpu-baseline', '--spectra', '32', '--full']
     d = _line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert d['n_gpus'] == 2 and d['steps'] == 3 and d['scaling'] == 'weak' and 'test_mode' in d['config']
     # weak scaling: every rank runs its own 32 spectra x 8 chains; the line counts the evaluations of both
@@ -122,21 +152,22 @@ def test_bare_gpus_2_launches_its_own_ranks():
 
 
 @pytest.mark.timeout(1800)
-def test_bench_eight_ranks_on_the_one_device():
-    """`bench.py --gpus 8` under the driver's launcher with all eight ranks on the box's single GPU over gloo: the 8-way partition
-    of the weak-scaling job (8 spectra x 8 chains = 64 units per rank), the `strong_scaling` leg (the same 64 spectra in total: 64
-    units per rank, one chain per workgroup) and the sharded round trip over 8 ranks.  Bookkeeping, not a rate."""
+def test_bench_four_ranks_on_the_one_device():
+    """`bench.py --gpus 4 --full` under the driver's launcher with all four ranks on the box's single GPU over gloo: the 4-way
+    partition of the weak-scaling job (8 spectra x 8 chains = 64 units per rank), the `strong_scaling` leg (the same 32 spectra in
+    total: 64 units per rank, one chain per workgroup) and the sharded round trip over 4 ranks.  Bookkeeping, not a rate.  Four
+    ranks, not the eight of a full node: with the launcher and this process, six processes hold the device at once."""
     env = dict(os.environ, BDRT_BENCH_ONE_DEVICE='1', BDRT_BENCH_ROUNDTRIP_TIMEOUT='600')
-    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr',
-           '127.0.0.1', '--master-port', '29547', os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2',
-           '--warmup', '1', '--rounds', '30', '--no-cpu-baseline', '--spectra', '8']
+    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr',
+           '127.0.0.1', '--master-port', '29547', os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--steps', '2',
+           '--warmup', '1', '--rounds', '30', '--no-cpu-baseline', '--spectra', '8', '--full']
     d = _line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500))
     c = d['config']
-    assert d['n_gpus'] == 8 and d['scaling'] == 'weak' and 'test_mode' in c
-    assert c['ranks_seen'] == 8 and c['rccl']['device_ids'] == [0] * 8
-    assert c['units_per_gpu'] == 64 and c['evals_in_timed_region'] == 8 * 64 * 30 * 2
+    assert d['n_gpus'] == 4 and d['scaling'] == 'weak' and 'test_mode' in c
+    assert c['ranks_seen'] == 4 and c['rccl']['device_ids'] == [0] * 4
+    assert c['units_per_gpu'] == 64 and c['evals_in_timed_region'] == 4 * 64 * 30 * 2
     ss = c['strong_scaling']
-    assert '64 spectra' in ss['workload'] and '(64 units per GPU)' in ss['workload'] and ss['sampler_kind_rank0'] == 1
+    assert '32 spectra' in ss['workload'] and '(64 units per GPU)' in ss['workload'] and ss['sampler_kind_rank0'] == 1
     assert ss['value'] > 1e4 and ss['steps'] >= 2
     rt = c['dist_roundtrip']
-    assert 'error' not in rt and rt['finite'] and rt['spectra'] == 64
+    assert 'error' not in rt and rt['finite'] and rt['spectra'] == 32

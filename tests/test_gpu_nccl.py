@@ -62,6 +62,8 @@ def _check_against_direct_run(got, world):
     p1 = Problem(pk['blocks'], pk['Z'][:1], pk['freq'], sigma_min=pk['sigma_min'], ups_alpha=1.0, ups_beta=0.1)
     d1, _, _ = sample_units(p1, 4, 8, 6, 99, c, spec=np.zeros(4, dtype=np.int32), chain_ids=np.arange(4, dtype=np.int32))
     assert np.array_equal(got['one_draws'], d1)                      # one spectrum, its four chains spread over the ranks
+    d3, _, _ = sample_units(p1, 3, 8, 6, 99, c, spec=np.zeros(3, dtype=np.int32), chain_ids=np.arange(3, dtype=np.int32))
+    assert np.array_equal(got['three_draws'], d3)                    # three chains: at world size 4 one rank has no unit
     p1.close()
     f, zs = _spectra(3)
     with warnings.catch_warnings():
@@ -83,14 +85,14 @@ def test_two_rccl_ranks_on_two_gpus_equal_a_direct_run(tmp_path):
 
 @pytest.mark.timeout(1500)
 def test_bench_two_rccl_ranks_on_two_gpus():
-    """`bench.py --gpus 2` as the driver launches it, on two devices over RCCL."""
+    """`bench.py --gpus 2 --full` as the driver launches it, on two devices over RCCL."""
     if _device_count() < 2:
         pytest.skip('one GPU visible')
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'BDRT_BENCH_ONE_DEVICE')}
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port',
            str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--rounds', '40', '--no-cpu-baseline',
-           '--spectra', '32']
+           '--spectra', '32', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
@@ -110,10 +112,11 @@ def test_the_same_rank_program_on_one_device_over_gloo(tmp_path):
 
 
 @pytest.mark.timeout(1800)
-def test_the_same_rank_program_with_eight_ranks_on_one_device_over_gloo(tmp_path):
-    """World size 8 -- the size of the node the driver scales to -- on the 1-GPU box: 5 spectra x 2 chains and 1 spectrum x 4
-    chains leave ranks with one unit or none (idle ranks must walk through every collective), `fit_many` shards 3 spectra
-    (6 units, 6 MAP rows) over 8 ranks.  Same assertions as with two ranks: everything equals one direct run."""
-    got = _run_ranks('gloo', 8, tmp_path)
-    assert [int(i) for i in got['device_ids']] == [0] * 8
-    _check_against_direct_run(got, 8)
+def test_the_same_rank_program_with_four_ranks_on_one_device_over_gloo(tmp_path):
+    """World size 4 on the 1-GPU box: 5 spectra x 2 chains leave ranks with two spectra or one, 1 spectrum x 4 chains one unit
+    per rank, 1 spectrum x 3 chains a rank with none (idle ranks must walk through every collective), `fit_many` shards 3 spectra
+    (6 units, 6 MAP rows) over 4 ranks.  Same assertions as with two ranks: everything equals one direct run.  Four ranks, not the
+    eight of a full node: with the launcher and this process, six processes hold the device at once."""
+    got = _run_ranks('gloo', 4, tmp_path)
+    assert [int(i) for i in got['device_ids']] == [0] * 4
+    _check_against_direct_run(got, 4)

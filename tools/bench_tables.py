@@ -1,5 +1,5 @@
 """The tables that accompany bench.py's headline (config.mid_occupancy, config.shapes, config.few_chains, cpu_baseline) in readable form.
-usage: python tools/bench_tables.py BENCH_LINE.json"""
+usage: python tools/bench_tables.py BENCH_LINE.json   (a line of `bench.py --full`: a plain run carries none of these)"""
 import json
 import sys
 
