@@ -74,6 +74,7 @@ SYMBOLS = [
     'bdrt_sample',
     'bdrt_gram', 'bdrt_qp_box', 'bdrt_qp_box_batch', 'bdrt_ridge',
     'bdrt_percentiles', 'bdrt_sampler_percentiles', 'bdrt_sampler_summary', 'bdrt_summary', 'bdrt_sampler_draws_dev',
+    'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
 ]
 
@@ -174,6 +175,8 @@ def load_library():
     lib.bdrt_sampler_percentiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.bdrt_sampler_summary.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]
     lib.bdrt_summary.argtypes = [vp, C.c_int, C.c_int, C.c_long, vp, vp, C.c_int, vp, vp]
+    lib.bdrt_sampler_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.bdrt_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, vp, vp]
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

@@ -107,6 +107,11 @@ int post_percentiles_device(const double *dX, int rows, int K, long ldx, const d
                             const double *q, int nq, double *out, const unsigned char *expcol = nullptr,
                             double *mean = nullptr);
 
+// HMC convergence diagnostics (bdrt_diag.hip) of G groups x M chains x N draws x C columns of DEVICE draws: element (g, m, t, c)
+// at dX[(g*M + m) * unit_stride + t * row_stride + c]; is_pos[C] (host, optional): exp() columns; outputs [G x C] on the host
+int diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M, int N,
+                        int C, double *mean, double *sd, double *n_eff, double *rhat, hipStream_t stream);
+
 // Levenberg-Marquardt Newton polish of n_fits points on the device (bdrt_newton.hip); x0 / x_out [n_fits][D] on the host
 int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
                          double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out);

@@ -89,8 +89,10 @@ class StanFit:
     """What `fit[name]` needs (reference inversion.py:2514-2519, :2560, :2702, :3096): post-warm-up draws of all
     chains merged, shape [chains*draws, ...]."""
 
-    def __init__(self, model, theta, lp, diag, chains, n_draws):
+    def __init__(self, model, theta, lp, diag, chains, n_draws, control=None, warmup=0):
         self._model = model
+        self.control = dict(control or {})      # adapt_delta / max_treedepth the run used (wording of the diagnostics)
+        self.warmup = int(warmup)
         self.theta = theta                      # [chains*draws, D] unconstrained
         self.lp = lp
         self.diagnostics = diag
@@ -113,6 +115,10 @@ class StanFit:
             return self.lp
         if name in ('Z_hat', 'sigma_tot'):
             return self._transformed()[name]
+        if name in self._model._from_Z_hat:
+            if not self._model._can_extract(name):      # e.g. Y_hat of a model that does not declare it
+                raise KeyError(name)
+            return self._model._extract_Z(self._transformed()['Z_hat'], self._params, name)
         return self._model._extract(self._params, name)
 
     def keys(self):
@@ -128,6 +134,16 @@ class StanFit:
         data = {k: np.array(self[k]) for k in self.keys()}
         data['lp__'] = np.array(self.lp)
         return SavedFit(data, self.chains, self.n_draws, self.diagnostics, np.array(self.theta))
+
+    def summary(self, pars=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
+        """pystan's `fit.summary()` (bayes_drt_amd.diagnostics.summary)."""
+        from . import diagnostics
+        return diagnostics.summary(self, pars, probs)
+
+    def stansummary(self, pars=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digits_summary=2):
+        """pystan's printed summary table as a string."""
+        from . import diagnostics
+        return diagnostics.stansummary(self, pars, probs, digits_summary)
 
 
 class SavedFit(dict):
@@ -151,6 +167,15 @@ class SavedFit(dict):
 
     def to_saved(self):
         return self
+
+    def summary(self, pars=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
+        """pystan's `fit.summary()` over the stored arrays (bayes_drt_amd.diagnostics.summary)."""
+        from . import diagnostics
+        return diagnostics.summary(self, pars, probs)
+
+    def stansummary(self, pars=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digits_summary=2):
+        from . import diagnostics
+        return diagnostics.stansummary(self, pars, probs, digits_summary)
 
     def __reduce__(self):
         return (SavedFit, (dict(self), self.chains, self.n_draws, self.diagnostics, self.theta))
@@ -178,6 +203,9 @@ class StanModel:
         if outl and fam == 'Series' and int(dat['N']) != nf:
             raise ValueError('Series outlier models take N = number of frequencies (inversion.py:1208-1211)')
         self.problem = Problem(blocks, Z, dat['freq'], **kw)
+        self._blocks = blocks
+        self._N = int(dat['N']) if 'N' in dat else 2 * nf
+        self._N_tilde = int(dat.get('N_tilde', 0))
         self._names = names
         self._lay = self.problem.layout()
         return self.problem
@@ -193,6 +221,39 @@ class StanModel:
         if self.problem.dat.outlier_mode:
             out.append('sigma_out')
         return out
+
+    # names computed from Z_hat (transformed parameters and generated quantities of the model texts; A_tilde = A, freq_tilde =
+    # freq in the Stan data of Inverter.fit, so the *_tilde quantities equal their fitted counterparts)
+    _from_Z_hat = frozenset(['Z_hat_re', 'Z_hat_im', 'Z_hat_tilde', 'Y_hat', 'Y_hat_re', 'Y_hat_im', 'Z_hat_p', 'Y_hat_tilde',
+                             'Y_hat_re_tilde', 'Y_hat_im_tilde', 'Z_hat_p_tilde'])
+
+    def _can_extract(self, name):
+        """Whether `StanFit[name]` provides this declared name (bayes_drt_amd.diagnostics.fit_columns)."""
+        n, fam = self._names, _family(self.model_name)[0]
+        if name in self.param_names() or name in n['q'] or name in n['dups'] or name in ('Z_hat_re', 'Z_hat_im'):
+            return True
+        if name == 'Z_hat_tilde':
+            return fam in ('Series', 'Parallel') and not _family(self.model_name)[2] and self._N_tilde == self._N
+        return fam == 'Parallel' and name in self._from_Z_hat
+
+    def _extract_Z(self, Zh, params, name):
+        """Names of `_from_Z_hat` from Z_hat [B x 2 Nf] (and, for the Parallel model, A x)."""
+        h = Zh.shape[1] // 2
+        if name in ('Z_hat_re', 'Z_hat_im'):
+            part = Zh[:, :h] if name == 'Z_hat_re' else Zh[:, h:]
+            return np.concatenate([part, part], axis=1)
+        if name == 'Z_hat_tilde':
+            return Zh
+        base = name[:-6] if name.endswith('_tilde') else name
+        Y = np.atleast_2d(params)[:, self._lay['x'][0]:self._lay['x'][0] + self.problem.Ks[0]] @ np.asarray(self._blocks[0]['A']).T
+        re, im = Y[:, :h], Y[:, h:]
+        if base == 'Y_hat': return Y
+        if base == 'Y_hat_re': return re
+        if base == 'Y_hat_im': return im
+        if base == 'Z_hat_p':
+            den = np.square(re) + np.square(im)
+            return np.concatenate([re / den, -im / den], axis=1)
+        raise KeyError(name)
 
     def _extract(self, params, name):
         """name -> array from constrained parameter rows [B x D] (transformed parameters by their Stan definitions)."""
@@ -222,6 +283,13 @@ class StanModel:
                 return ret(0.5 * (u[:, 1:-1] - 0.5 * (u[:, :-2] + u[:, 2:])) / u[:, 1:-1])
             for i, dn in enumerate(n['d'][b]):
                 if name == dn: return ret(p[:, lay['d'][b] + i])
+            if name == n['q'][b]:
+                # q = sqrt(d0 (L0 x)^2 + d1 (L1 x)^2 + d2 (L2 x)^2) on the block's raw coefficients (model texts)
+                blk = self._blocks[b]
+                acc = 0.0
+                for i, key in enumerate(('L0', 'L1', 'L2')):
+                    acc = acc + p[:, lay['d'][b] + i][:, None] * np.square(xs @ np.asarray(blk[key]).T)
+                return ret(np.sqrt(acc))
         if P.dat.outlier_mode:
             so = lay['so']
             if name == 'sigma_out_raw':
@@ -348,7 +416,8 @@ class StanModel:
         draws, lp, diag = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
                                        chain_ids=chain_ids, rounds_per_launch=rounds_per_launch)
         theta = draws.reshape(chains * n_draws, P.D)
-        return StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws)
+        return StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
+                       control=dict(adapt_delta=ctrl.adapt_delta, max_treedepth=ctrl.max_treedepth), warmup=warmup)
 
 
 class DeviceArray:
@@ -452,6 +521,12 @@ class Sampler:
             raise _lib.BdrtError('a chain found no finite initial point in 100 attempts')
         return draws, lp, dl
 
+    def diagnostics(self, unit_lo, unit_hi, chains):
+        """(mean, sd, n_eff, Rhat), each [groups x D], of the CONSTRAINED parameters over units [unit_lo, unit_hi) in groups of
+        `chains` consecutive units, reduced in HBM in one launch (bdrt_sampler_diagnostics)."""
+        from .diagnostics import sampler_diagnostics
+        return sampler_diagnostics(self, unit_lo, unit_hi, chains)
+
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""
         p = self._lib.bdrt_sampler_draws_dev(self.handle)
@@ -470,12 +545,17 @@ class Sampler:
 
 
 def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, chain_ids=None, init_theta=None,
-                 rounds_per_launch=None):
+                 rounds_per_launch=None, diagnostics_chains=None):
     """Run n_units chains (unit u: spectrum spec[u], RNG stream (seed, chain_ids[u])) to completion on the GPU.
-    Returns draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain diagnostics."""
+    Returns draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain diagnostics.
+    diagnostics_chains=M: also reduce the convergence diagnostics of the constrained parameters, groups of M consecutive units,
+    in one launch while the sampler still holds the draws; a fourth item (mean, sd, n_eff, Rhat), each [n_units / M, D]."""
     with Sampler(problem, n_units, warmup, n_draws, seed, ctrl, spec=spec, chain_ids=chain_ids, init_theta=init_theta) as smp:
         smp.run(rounds_per_launch)
-        return smp.results()
+        res = smp.results()
+        if diagnostics_chains:
+            res = res + (smp.diagnostics(0, n_units, diagnostics_chains),)
+        return res
 
 
 def optimize_batch(problem, theta0, spec=None, max_iter=50000, **opts):

@@ -750,7 +750,7 @@ class Inverter:
     def fit(self, frequencies, Z, part='both', scale_Z=True, nonneg=False, outliers=False, check_outliers=True,
             init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
             mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
-            model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None):
+            model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True):
         """Fit the distribution(s) with the calibrated hierarchical Bayesian model: mode='optimize' (MAP) or
         'sample' (NUTS).  Arguments as in the reference (:1072-1152), plus two that only concern mode='optimize':
 
@@ -763,7 +763,10 @@ class Inverter:
             n_starts=k > 1: the designated start, the other kind of start if there is one, then further random draws.
         algorithm : None / 'LBFGS+Newton' (default) -- the device-resident Newton iteration to a stationary point;
             'LBFGS' -- Stan's L-BFGS(5) with Stan's line search and termination tests alone, i.e. the kind of iterate the
-            reference's `optimizing` call returns."""
+            reference's `optimizing` call returns.
+        check_diagnostics : mode='sample' only -- True (default): pystan's check after sampling (n_eff, split R-hat,
+            divergences, tree depth; n_eff and R-hat skipped above 1000 flat names), logged at WARNING to
+            logging.getLogger('bayes_drt_amd') (bayes_drt_amd.diagnostics); False: no check."""
         self._fit_argument_checks(part, mode, fitY, SA, SASY, n_starts, algorithm)
         job = self._fit_prepare(frequencies, Z, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                 inductance_scale, outlier_lambda, mode, add_stan_data, model_str, fitY, SA, SASY, n_starts)
@@ -775,6 +778,9 @@ class Inverter:
         else:
             self._sample_result = model.sampling(dat, warmup=warmup, iter=warmup + samples, chains=chains,
                                                  seed=random_seed, init=job['init'], control=dict(self._NUTS_CONTROL))
+            if check_diagnostics:
+                from . import diagnostics
+                diagnostics.auto_check(self._sample_result, diagnostics.flat_parameter_count(job['model_str'], dat))
         self._fit_finish(job, mode, sigma_min, check_outliers)
 
     _NUTS_CONTROL = {'adapt_delta': 0.9, 'adapt_t0': 10}        # reference :1221
@@ -834,7 +840,7 @@ class Inverter:
     def fit_many(self, frequencies, Z_list, part='both', scale_Z=True, nonneg=False, outliers=False, check_outliers=True,
                  init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
                  mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
-                 model_str=None, n_starts=None, algorithm=None, group=None):
+                 model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True):
         """The fits `[copy(self).fit(frequencies, Z, ...) for Z in Z_list]` -- the reference's own workload is such a loop
         over spectra measured on one frequency grid (code_EchemActa/Run fits.ipynb cells 4-5, inversion.py:1072-1081,
         :1218-1221) -- as ONE batch: one shared problem in HBM (the matrices are those of the common grid), every
@@ -851,7 +857,9 @@ class Inverter:
         for the noiseless spectrum, 0.002 otherwise).  Spectra that share grid, basis, model and options are one batch -- one
         problem in HBM, one engine call --, the others further batches of the same call; the list comes back in input order.
         Returns a list of Inverter objects (shallow copies of this one) carrying the fit attributes of `fit`, readable
-        through `predict_*`, `coef_percentile`, ...; this instance itself is left as it was."""
+        through `predict_*`, `coef_percentile`, ...; this instance itself is left as it was.
+        check_diagnostics (mode='sample'): pystan's check of every spectrum's chains, as `fit` runs it; the parameters of the
+        whole batch are reduced in one launch on the sampler's device draws, the transformed parameters in one more."""
         self._fit_argument_checks(part, mode, False, False, False, n_starts, algorithm)
         views, jobs = self._batch_jobs(frequencies, Z_list, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                        inductance_scale, outlier_lambda, mode, add_stan_data, model_str, n_starts)
@@ -865,7 +873,7 @@ class Inverter:
             order.setdefault(self._batch_key(job), []).append(i)
         for idx in order.values():
             self._fit_batch([views[i] for i in idx], [jobs[i] for i in idx], mode, random_seed, max_iter, warmup, samples,
-                            chains, algorithm, group)
+                            chains, algorithm, group, check_diagnostics, idx)
         for inv, job in zip(views, jobs):
             inv._fit_finish(job, mode, job['sigma_min'], check_outliers)
         return views
@@ -953,7 +961,8 @@ class Inverter:
         return jobs[0]['model_str'], self._stack_stan_data(jobs)
 
     @staticmethod
-    def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group):
+    def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics=False,
+                   index=None):
         """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view."""
         import ctypes as C
         from . import engine, parallel
@@ -1023,11 +1032,17 @@ class Inverter:
         if any(not (isinstance(job['init'], str) and job['init'] == 'random') for job in jobs):
             init_theta = np.vstack([model._init_theta(job['init'], chains, random_seed) for job in jobs])
         control = dict(Inverter._NUTS_CONTROL)
+        from . import diagnostics
+        flat = diagnostics.flat_parameter_count(jobs[0]['model_str'], dat)
+        param_stats = None
         if world > 1:
             blocks, kw, _ = engine.blocks_from_dat(model.model_name, dat)
             pk = dict(kw, blocks=blocks, Z=np.asarray(dat['Z'], dtype=float), freq=np.asarray(dat['freq'], dtype=float))
+            want = bool(check_diagnostics and flat <= diagnostics.MAX_FLAT)
             res = parallel.sample_sharded(pk if dist.get_rank(group) == 0 else None, ns, chains, warmup, n_draws, seed=random_seed,
-                                          control=control, group=group, gather='draws', init_theta=init_theta)
+                                          control=control, group=group, gather='draws', init_theta=init_theta, diagnostics=want)
+            if want:
+                param_stats = (None, None, res['n_eff'], res['Rhat'])
             draws, lp = res['draws'], res['lp']
             diag = [dict(n_leapfrog=int(r[0]), n_divergent=int(r[1]), n_max_treedepth=int(r[2]), stepsize=float(r[3]),
                          mean_accept=float(r[4])) for r in res['stats']]
@@ -1036,12 +1051,20 @@ class Inverter:
             P._lib.bdrt_nuts_defaults(C.byref(ctrl))
             for k, v in control.items():
                 setattr(ctrl, k, v)
-            draws, lp, diag = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
-                                                  init_theta=init_theta)
+            want = chains if (check_diagnostics and flat <= diagnostics.MAX_FLAT) else None
+            res = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
+                                      init_theta=init_theta, diagnostics_chains=want)
+            draws, lp, diag = res[:3]
+            if want:
+                param_stats = res[3]
+        ctl = dict(adapt_delta=control['adapt_delta'], max_treedepth=control.get('max_treedepth', 10))
         for i, inv in enumerate(views):
             u0, u1 = i * chains, (i + 1) * chains
             inv._sample_result = engine.StanFit(model, draws[u0:u1].reshape(chains * n_draws, P.D), lp[u0:u1].reshape(-1),
-                                                diag[u0:u1], chains, n_draws)
+                                                diag[u0:u1], chains, n_draws, control=ctl, warmup=warmup)
+        # with several ranks only rank 0 runs the check (and logs): every rank holds the same results
+        if check_diagnostics and (world == 1 or dist.get_rank(group) == 0):
+            diagnostics.batch_check([inv._sample_result for inv in views], flat, param_stats, index)
 
     @staticmethod
     def _resolve_deferred_ridge_starts(views, jobs):

@@ -186,6 +186,16 @@ class GpuWorker:
     def is_pos(self):
         return self.problem.is_pos
 
+    def diagnostics(self, unit_lo, unit_hi, chains):
+        """(mean, sd, n_eff, Rhat) [spectra x D] of this rank's units [unit_lo, unit_hi), reduced on the sampler's device draws."""
+        return self.sampler.diagnostics(unit_lo, unit_hi, chains)
+
+    @staticmethod
+    def reduce_diagnostics(blocks, chains, is_pos):
+        """The same reduction on host-resident unconstrained draws [spectra, chains * draws, D] (bdrt_diagnostics)."""
+        from .diagnostics import column_diagnostics
+        return column_diagnostics(blocks, chains, is_pos=is_pos)
+
     @staticmethod
     def reduce(block, is_pos, q):
         """(mean [D], pct [len(q), D]) of the constrained parameters over the rows of `block` (unconstrained draws): the
@@ -237,7 +247,7 @@ def _unpack_problem(flat):
 
 
 def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234, control=None, group=None,
-                   worker_cls=None, gather='draws', q=(2.5, 50.0, 97.5), init_theta=None):
+                   worker_cls=None, gather='draws', q=(2.5, 50.0, 97.5), init_theta=None, diagnostics=False):
     """Sample `chains` chains for each of `n_spectra` spectra on all ranks of the process group.
 
     problem_kwargs (needed on rank 0 only; other ranks may pass None): dict(blocks=[...], Z=[n_spectra x 2nf], freq=...,
@@ -250,7 +260,10 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
     spectrum are spread over ranks (fewer spectra than ranks) the summary needs all of them, so the draws are gathered
     in that case regardless.
     init_theta (rank 0; optional): [n_units, D] unconstrained start points in unit order (Stan `init=` values; default: the
-    sampler's own random starts); each rank receives the rows of its units with the scatter of the spectra."""
+    sampler's own random starts); each rank receives the rows of its units with the scatter of the spectra.
+    diagnostics=True adds n_eff [n_spectra, D] and Rhat [n_spectra, D]: the convergence diagnostics of the constrained
+    parameters per spectrum (bayes_drt_amd.diagnostics), each rank reducing its own spectra in one launch on its sampler's
+    device draws; when the chains of a spectrum are spread over ranks, every rank reduces the gathered draws instead."""
     if gather not in ('draws', 'summary'):
         raise ValueError("gather must be 'draws' or 'summary'")
     dist = _dist()
@@ -323,8 +336,11 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
     # ranks without work learn D (and which parameters are <lower=0>) from the first rank that has some
     owners = [r for r in range(world) if counts[r] > 0]
     if not owners:
-        return dict(stats=np.zeros((0, 5)), lp=np.zeros((0, n_draws)), mean=np.zeros((0, 0)), pct=np.zeros((0, len(q), 0)),
-                    draws=np.zeros((0, n_draws, 0)))
+        empty = dict(stats=np.zeros((0, 5)), lp=np.zeros((0, n_draws)), mean=np.zeros((0, 0)), pct=np.zeros((0, len(q), 0)),
+                     draws=np.zeros((0, n_draws, 0)))
+        if diagnostics:
+            empty.update(n_eff=np.zeros((0, 0)), Rhat=np.zeros((0, 0)))
+        return empty
     dd = [(D, np.asarray(worker.is_pos(), dtype=bool).tolist()) if worker is not None else None]
     dist.broadcast_object_list(dd, src=owners[0], group=group)
     D, is_pos = int(dd[0][0]), np.asarray(dd[0][1], dtype=bool)
@@ -344,6 +360,13 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
             loc[i, 0], loc[i, 1:] = m, p
         summ = gather_rows(loc, [c // chains for c in counts], group)
         out['mean'], out['pct'] = summ[:, 0], summ[:, 1:]
+        if diagnostics:
+            dl = np.zeros((ns_local, 2, D))
+            if ns_local:
+                _, _, ne, rh = worker.diagnostics(0, u1 - u0, chains)
+                dl[:, 0], dl[:, 1] = ne, rh
+            dg = gather_rows(dl, [c // chains for c in counts], group)
+            out['n_eff'], out['Rhat'] = dg[:, 0], dg[:, 1]
     else:
         # the chains of a spectrum are on several ranks: reduce the gathered draws (every rank, same arithmetic)
         mean = np.empty((n_spectra, D)); pct = np.empty((n_spectra, len(q), D))
@@ -351,6 +374,9 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
             block = out['draws'][sidx * chains:(sidx + 1) * chains].reshape(chains * n_draws, D)
             mean[sidx], pct[sidx] = cls.reduce(block, is_pos, q)
         out['mean'], out['pct'] = mean, pct
+        if diagnostics:
+            blocks = out['draws'].reshape(n_spectra, chains * n_draws, D)
+            _, _, out['n_eff'], out['Rhat'] = cls.reduce_diagnostics(blocks, chains, is_pos)
         if gather == 'summary':
             out.pop('draws')
     if worker is not None:

@@ -307,6 +307,20 @@ int bdrt_sampler_summary(bdrt_sampler *s, int unit_lo, int unit_hi, const double
 /* the same reduction on host-resident draws X [rows x K] (row stride ldx): is_pos[K] flags the exp() columns (NULL: none) */
 int bdrt_summary(const double *X, int rows, int K, long ldx, const unsigned char *is_pos, const double *q, int nq,
                  double *mean, double *pct);
+/* HMC convergence diagnostics (pystan's `summary` / `check_hmc_diagnostics`; definitions: tests/diag_numpy.py): for every
+ * column, over the chains of one group (a group = the chains of one spectrum), the mean and sd (ddof = 1) of all draws, the
+ * non-split effective sample size n_eff (Geyer's initial positive + monotone sequence, Stan 2.19) and the split R-hat.
+ * A column with a non-finite draw, or whose draws are all equal, gives n_eff = Rhat = NaN; N < 4 draws give n_eff = NaN.
+ * Bit-reproducible (fixed summation order); both entry points run the same kernel, so equal draws give equal bits.
+ * Draws of units [unit_lo, unit_hi) of a sampler, on the CONSTRAINED scale (<lower=0> parameters are exp(theta)), grouped by
+ * chains_per_group consecutive units: G = (unit_hi - unit_lo) / chains_per_group groups x D columns.  Outputs [G x D]
+ * (any may be NULL).  The draws are not copied to the host. */
+int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, double *mean, double *sd,
+                             double *n_eff, double *rhat);
+/* the same reduction on host-resident draws X [G groups][M chains][N draws][C columns], rows of stride ldx >= C doubles;
+ * is_pos[C] flags the exp() columns (NULL: none); outputs [G x C].  M <= 64. */
+int bdrt_diagnostics(const double *X, int G, int M, int N, int C, long ldx, const unsigned char *is_pos, double *mean,
+                     double *sd, double *n_eff, double *rhat);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
