@@ -76,6 +76,7 @@ SYMBOLS = [
     'bdrt_percentiles', 'bdrt_sampler_percentiles', 'bdrt_sampler_summary', 'bdrt_summary', 'bdrt_sampler_draws_dev',
     'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
+    'bdrt_debug_hessian', 'bdrt_debug_hessian_lin',
 ]
 
 
@@ -142,6 +143,8 @@ def load_library():
     lib.bdrt_build_L.argtypes = [vp, C.c_int, C.c_double, vp, vp]
     lib.bdrt_build_L_rect.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, vp, C.c_int, vp]
     lib.bdrt_build_M.argtypes = [vp, C.c_int, C.c_double, vp, C.c_int, vp]
+    lib.bdrt_debug_hessian.argtypes = [vp, vp, C.c_int, vp]
+    lib.bdrt_debug_hessian_lin.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.bdrt_opt_defaults.argtypes = [C.POINTER(OptOptions)]
     lib.bdrt_opt_defaults.restype = None
     lib.bdrt_optimize.argtypes = [vp, vp, vp, C.c_int, C.POINTER(OptOptions), vp, vp]

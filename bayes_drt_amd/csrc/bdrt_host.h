@@ -116,8 +116,9 @@ int diagnostics_to_host(const double *dX, long unit_stride, long row_stride, con
 int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
                          double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out);
 
-// closed-form Hessian at one point (bdrt_newton_hess.h; tests): 1 when the problem has none
-int hessian_at_point(Problem &P, const double *theta, int spec, double *H_out);
+// closed-form Hessian at one point (bdrt_newton_hess.h; tests): 1 when the problem has none.  lin: the coefficients on the linear
+// scale (Series_pos only, else 1); held_out [D] (optional): the coefficients held at their floor
+int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double *H_out, double *held_out);
 
 }  // namespace bdrt
 

@@ -175,10 +175,17 @@ int bdrt_optimize(bdrt_problem *p, const double *init_theta, const int *spec, in
 
 // closed-form Hessian of the log-posterior (no Jacobian) at one unconstrained point, as the Newton iteration uses it (tests):
 // H_out [D x D] row-major; returns 1 when the model has no closed form here (the iteration then differences gradients)
+// lin = 1: with the coefficients of a Series_pos model on the linear scale (the iteration's own rule picks the branch: lam = 0);
+// held_out [D] (may be null): 1.0 for the coefficients held at their floor.  1 as well when lin is asked of a model without <lower=0> coefficients
+int bdrt_debug_hessian_lin(bdrt_problem *p, const double *theta, int spec, int lin, double *H_out, double *held_out)
+{
+    if (!p || !theta || !H_out || spec < 0 || spec >= p->impl.dev.n_spectra || lin < 0 || lin > 1) { set_error("bdrt_debug_hessian_lin: bad arguments"); return -1; }
+    return hessian_at_point(p->impl, theta, spec, lin, H_out, held_out);
+}
+
 int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H_out)
 {
-    if (!p || !theta || !H_out || spec < 0 || spec >= p->impl.dev.n_spectra) { set_error("bdrt_debug_hessian: bad arguments"); return -1; }
-    return hessian_at_point(p->impl, theta, spec, H_out);
+    return bdrt_debug_hessian_lin(p, theta, spec, 0, H_out, nullptr);
 }
 
 }  // extern "C"

@@ -861,10 +861,14 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
     return 0;
 }
 
-// the closed-form Hessian at ONE point (tests): H_out [D][D] row-major on the host; 1 when the problem has no closed form here
-int hessian_at_point(Problem &P, const double *theta, int spec, double *H_out)
+// the closed-form Hessian at ONE point (tests): H_out [D][D] row-major on the host; 1 when the problem has no closed form here.
+// lin: the coefficients on the linear scale, as the iteration takes them once its damping has dropped (lam stays 0 here, so the
+// kernels' own rule selects the branch from lin_ok); 1 as well when that is asked of a model whose coefficients are free.
+// held_out [D] (optional): the workspace's `act` slots, 1.0 for a coefficient held at its floor.
+int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double *H_out, double *held_out)
 {
     if (!hess_analytic_ok(P.dev)) return 1;
+    if (lin && !P.dev.blk[0].is_pos) return 1;
     const int D = P.dev.D, Dp = (D + 15) & ~15;
     BDRT_HIP(hipSetDevice(P.device));
     std::vector<void *> owned;
@@ -878,6 +882,7 @@ int hessian_at_point(Problem &P, const double *theta, int spec, double *H_out)
     NewtonBufs b;
     memset(&b, 0, sizeof(b));
     b.D = D; b.Dp = Dp; b.analytic = 1; b.dP = (const DevProblem *)P.d_dev;
+    b.lin_ok = lin ? 1 : 0;
     const HessLayout hlay(P.dev.nf, P.dev.blk[0].K);
     int *d_act = nullptr, *d_spec = nullptr;
     double *d_lp = nullptr;
@@ -904,6 +909,7 @@ int hessian_at_point(Problem &P, const double *theta, int spec, double *H_out)
     HP_HIP(hipGetLastError());
     std::vector<double> hh((size_t)Dp * Dp);
     HP_HIP(hipMemcpyAsync(hh.data(), b.H, hh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (held_out) HP_HIP(hipMemcpyAsync(held_out, b.hws + hlay.act, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, st));
     HP_HIP(hipStreamSynchronize(st));
     // (the kernels write the block lower triangle: mirror it)
     for (int i = 0; i < D; ++i)

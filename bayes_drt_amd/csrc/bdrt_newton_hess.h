@@ -73,18 +73,20 @@ __device__ __forceinline__ double hess_A(const DevBlock &B, int nf, int part, in
     return B.Ad[((size_t)part * nf + n) * B.K + m];
 }
 
-// whether the closed form applies to a problem (single series distribution, no outlier model, banded Toeplitz L, not streamed, and
-// the fill kernel's LDS tile fits)
+constexpr int HP_NT = 512;
+
+// whether the closed form applies to a problem (single series distribution, no outlier model, banded Toeplitz L, not streamed,
+// the fill kernel's LDS tile fits, and the tile is no wider than the 2 HP_NT columns the fill kernel's threads own)
 __host__ inline bool hess_analytic_ok(const DevProblem &P)
 {
     if (!(P.nblocks == 1 && !P.blk[0].is_parallel && P.outlier_mode == 0 && !P.use_x_sum && P.blk[0].toep && !P.big &&
           (P.blk[0].tg || P.blk[0].Ad) && P.nf <= 256)) return false;
     const size_t nf = P.nf, K = P.blk[0].K;
+    if (((2 * K + 9 + 15) & ~(size_t)15) > 2 * HP_NT) return false;          // Dp: see NH in hess_fill
     const size_t fill = 35 * nf + 40 + 2 * (nf + K) + 16 * ((2 * K + 9 + 15) & ~(size_t)15);
     return fill * sizeof(double) <= 150 * 1024;
 }
 
-constexpr int HP_NT = 512;
 static_assert(2 * MAXBW + 1 == 13, "the LDS copy of the band coefficients is laid out as [3][13]");
 
 // ---- prep: one workgroup per fit -------------------------------------------------------------------------------------------
@@ -449,7 +451,11 @@ __device__ inline bool hess_fill(const HessArgs &a, int f, int r0, double lam, d
     // columns per frequency serve 64 multiply-adds instead of 32 (the product is bound by the LDS bandwidth of those reads).
     bool bad = false;
     const int ncol = r0 + 16 < Dp ? r0 + 16 : Dp;
-    const int NH = ((ncol + 1) / 2 + 63) & ~63;                 // 64, 128 or 192 (Dp <= 384 here; wider: 256 and one group)
+    // NH = 64 .. 512: up to 256 it divides the workgroup into NG >= 2 groups; 320, 384, 448 and 512 leave one group.  A thread owns two
+    // columns and nothing loops over j0, so the pairs (j0, j0 + NH), j0 < min(NH, HP_NT), reach every column only while ncol <= 2 HP_NT:
+    // wider problems are REJECTED by hess_analytic_ok (Dp <= 1024; they keep the finite-difference Hessian), not looped over here.
+    // (Today the banded L path stops at K = 192, Dp = 400: NH <= 256 in every admitted problem, tests/test_gpu_hessian.py.)
+    const int NH = ((ncol + 1) / 2 + 63) & ~63;
     // The product is bound by the LATENCY of its LDS reads while few waves run it, so the frequencies are split over NG groups of NH
     // threads (all eight waves busy); the groups' partial sums meet in the tile in a fixed order.
     const int NG = HP_NT / NH > 0 ? HP_NT / NH : 1;

@@ -331,6 +331,18 @@ int bdrt_device_count(void);
 int bdrt_set_device(int dev);
 const char *bdrt_version(void);
 
+/* ---- debug (tests): pieces of the optimizer at one point ------------------------------------------------
+ * The closed-form Hessian of the log-posterior (optimize mode: no Jacobian term) at the unconstrained point theta [D] for
+ * spectrum `spec`, as the Newton iteration of bdrt_optimize builds it: H_out [D x D] row-major on the host.
+ * lin = 0: every <lower=0> parameter on the log scale.  lin = 1 (nonnegative coefficients only): the coefficients on the
+ * LINEAR scale z = x with their floor, 1e-14 of the largest one; a coefficient within twice the floor whose gradient points
+ * below it is held: held_out [D] (may be NULL) is 1.0 there and 0.0 elsewhere, and H has -1 on its diagonal entry and 0 in
+ * the rest of its row and column.  Returns 1 when the model has no closed form here (the iteration then differences
+ * gradients), or when lin = 1 is asked of a model whose coefficients are free. */
+int bdrt_debug_hessian_lin(bdrt_problem *p, const double *theta, int spec, int lin, double *H_out, double *held_out);
+/* the same with lin = 0 */
+int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,14 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
+def test_debug_hessian_entries_are_declared_and_exported():
+    """the two test entries of the closed-form Hessian (tests/test_gpu_hessian.py) are part of the declared ABI"""
+    lib = _lib.load_library()
+    for name in ('bdrt_debug_hessian', 'bdrt_debug_hessian_lin'):
+        assert name in _declared() and name in _lib.SYMBOLS and hasattr(lib, name), name
+    assert len(lib.bdrt_debug_hessian_lin.argtypes) == len(lib.bdrt_debug_hessian.argtypes) + 2
+
+
 def test_struct_sizes_match_header():
     # bdrt_dat: 2 int + 3*3 int + 3 double + 4*3 ptr + ptr + int + ptr + 4 double + int + 3 double + int + double
     assert C.sizeof(_lib.Dat) % 8 == 0
