@@ -72,7 +72,7 @@ SYMBOLS = [
     'bdrt_sampler_run', 'bdrt_sampler_results', 'bdrt_sampler_tail_units', 'bdrt_sampler_compactions', 'bdrt_sampler_kind', 'bdrt_sampler_total_leapfrogs', 'bdrt_sampler_kernel_time',
     'bdrt_sampler_phase_profile',
     'bdrt_sample',
-    'bdrt_gram', 'bdrt_qp_box', 'bdrt_qp_box_batch', 'bdrt_ridge',
+    'bdrt_gram', 'bdrt_gram_batch', 'bdrt_qp_box', 'bdrt_qp_box_batch', 'bdrt_ridge', 'bdrt_ridge_ex',
     'bdrt_percentiles', 'bdrt_sampler_percentiles', 'bdrt_sampler_summary', 'bdrt_summary', 'bdrt_sampler_draws_dev',
     'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
@@ -174,6 +174,8 @@ def load_library():
     lib.bdrt_qp_box.argtypes = [vp, vp, vp, C.c_int, vp, vp]
     lib.bdrt_qp_box_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     lib.bdrt_ridge.argtypes = [C.POINTER(RidgeOptions), C.c_int, C.c_int] + [vp] * 20
+    lib.bdrt_gram_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    lib.bdrt_ridge_ex.argtypes = [C.POINTER(RidgeOptions), vp, vp, C.c_int, C.c_int] + [vp] * 20
     lib.bdrt_percentiles.argtypes = [vp, C.c_int, C.c_int, C.c_long, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.bdrt_sampler_percentiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.bdrt_sampler_summary.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]

@@ -491,11 +491,13 @@ __global__ __launch_bounds__(QP_NT) void qp_box_kernel(const double *__restrict_
 // ---- hyper-lambda ridge: the whole outer loop of Inverter.ridge_fit on the device ---------------------------------------------
 // (reference bayes_drt/inversion.py:518-740; lambda updates :947-983; see include/bdrt.h bdrt_ridge for the arithmetic)
 struct RidgeArgs {
-    int n, K, off, penalty, max_iter, hyper_lambda, zero_delta1;
-    double xtol, hl_fbeta;
+    int n, K, off, penalty, max_iter, hyper_lambda;
+    double xtol;
     double reg_ord[3];
     const double *G, *qbase;     // [ng][n][n], [ng][n]
     const int *gsel;             // [nb]
+    const unsigned char *zero_delta1_g;   // [ng]  data part g leaves entry 1 out of the convergence test
+    const double *hl_fbeta_b;    // [nb]       <= 0: analytic discrete update
     const double *base;          // [3][n][n]
     const double *Ls;            // [3][K][n] (discrete penalty)
     const double *lo;            // [n]
@@ -522,7 +524,8 @@ __global__ __launch_bounds__(QP_NT) void ridge_kernel(RidgeArgs a)
     const double *G = a.G + (size_t)a.gsel[b] * n * n, *q = a.qbase + (size_t)a.gsel[b] * n;
     double *P = a.Pwork + (size_t)b * n * n;
     double *Mw = LDSM ? nullptr : a.Mwork + (size_t)b * ((size_t)n * (n + 1) / 2);
-    const double l0 = a.lambda0[b];
+    const double l0 = a.lambda0[b], hl_fbeta = a.hl_fbeta_b[b];
+    const bool zero_delta1 = a.zero_delta1_g[a.gsel[b]] != 0;
     for (int i = tid; i < n; i += QP_NT) {
         coef[i] = a.x0 ? a.x0[(size_t)b * n + i] : 1e-6;
         lam[i] = l0; lam[np + i] = l0; lam[2 * np + i] = l0;
@@ -551,11 +554,11 @@ __global__ __launch_bounds__(QP_NT) void ridge_kernel(RidgeArgs a)
                         if (lane == 0) tmp[r] = t * t;
                     }
                     __syncthreads();
-                    if (a.hl_fbeta > 0.0) {
+                    if (hl_fbeta > 0.0) {
                         double mx = 0.0;
                         for (int r = tid; r < K; r += QP_NT) mx = fmax(mx, tmp[r]);
                         mx = -block_min(-mx, red);
-                        for (int r = tid; r < K; r += QP_NT) lv[off + r] = l0 / (tmp[r] / (mx * a.hl_fbeta) + 1.0);
+                        for (int r = tid; r < K; r += QP_NT) lv[off + r] = l0 / (tmp[r] / (mx * hl_fbeta) + 1.0);
                     } else {
                         for (int r = tid; r < K; r += QP_NT) lv[off + r] = 1.0 / (tmp[r] / (beta - 1.0) + 1.0 / lam0);
                     }
@@ -613,7 +616,7 @@ __global__ __launch_bounds__(QP_NT) void ridge_kernel(RidgeArgs a)
         for (int i = tid; i < n; i += QP_NT) {
             c1 += coef[i] * (0.5 * tmp[i] + q[i]);
             double dl = (coef[i] - prev[i]) / prev[i];
-            if (i == 1 && a.gsel[b] < 31 && ((a.zero_delta1 >> a.gsel[b]) & 1)) dl = 0.0;     // (a property of the fit's data part)
+            if (i == 1 && zero_delta1) dl = 0.0;     // (a property of the fit's data part)
             dl = fabs(dl);
             if (dl != dl) dnan += 1.0; else dsum += dl;
         }
@@ -703,12 +706,13 @@ int bdrt_qp_box_batch(const double *P, const double *q, const double *lo, int n,
 }
 
 
-int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, const double *qbase, const int *gsel,
-               const double *base, const double *Ls, const double *lo, const double *lambda0, const double *lam0s,
-               const double *betas, const double *x0, double *coef, double *lam, double *cost, double *fun, int *iters,
-               int *flags, double *hist_coef, double *hist_lam, double *hist_fun, double *hist_cost)
+int bdrt_ridge_ex(const bdrt_ridge_options *opt, const unsigned char *zero_delta1_g, const double *hl_fbeta_b, int nb, int ng,
+                  const double *G, const double *qbase, const int *gsel, const double *base, const double *Ls, const double *lo,
+                  const double *lambda0, const double *lam0s, const double *betas, const double *x0, double *coef, double *lam,
+                  double *cost, double *fun, int *iters, int *flags, double *hist_coef, double *hist_lam, double *hist_fun,
+                  double *hist_cost)
 {
-    if (!opt || nb < 1 || ng < 1 || !G || !qbase || !gsel || !base || !lambda0 || !lam0s || !betas || !coef || opt->n < 1 ||
+    if (!opt || !zero_delta1_g || !hl_fbeta_b || nb < 1 || ng < 1 || !G || !qbase || !gsel || !base || !lambda0 || !lam0s || !betas || !coef || opt->n < 1 ||
         opt->max_iter < 1 || (opt->penalty == 0 && opt->hyper_lambda && (!Ls || opt->K < 1)) || opt->off < 0 || opt->off > opt->n) {
         set_error("bdrt_ridge: bad arguments");
         return -1;
@@ -737,12 +741,14 @@ int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, c
     RidgeArgs a;
     memset(&a, 0, sizeof(a));
     a.n = n; a.K = K; a.off = opt->off; a.penalty = opt->penalty; a.max_iter = mi; a.hyper_lambda = opt->hyper_lambda;
-    a.zero_delta1 = opt->zero_delta1; a.xtol = opt->xtol; a.hl_fbeta = opt->hl_fbeta;
+    a.xtol = opt->xtol;
     for (int o = 0; o < 3; ++o) a.reg_ord[o] = opt->reg_ord[o];
     const void *d = nullptr;
     RG_HIP(up(G, (size_t)ng * n * n * 8, &d)); a.G = (const double *)d;
     RG_HIP(up(qbase, (size_t)ng * n * 8, &d)); a.qbase = (const double *)d;
     RG_HIP(up(gsel, (size_t)nb * sizeof(int), &d)); a.gsel = (const int *)d;
+    RG_HIP(up(zero_delta1_g, (size_t)ng, &d)); a.zero_delta1_g = (const unsigned char *)d;
+    RG_HIP(up(hl_fbeta_b, (size_t)nb * 8, &d)); a.hl_fbeta_b = (const double *)d;
     RG_HIP(up(base, (size_t)3 * n * n * 8, &d)); a.base = (const double *)d;
     if (Ls) { RG_HIP(up(Ls, (size_t)3 * K * n * 8, &d)); a.Ls = (const double *)d; }
     if (lo) { RG_HIP(up(lo, (size_t)n * 8, &d)); a.lo = (const double *)d; }
@@ -804,6 +810,21 @@ int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, c
     for (int b = 0; b < nb; ++b)
         if (hfl[b] == -3) { set_error("bdrt_ridge: KKT matrix of fit %d not positive definite", b); return -3; }
     return 0;
+}
+
+// the entry with one flag word and one hl_fbeta per launch: bit g of opt->zero_delta1 for the data parts g < 31 (further
+// parts: not set), opt->hl_fbeta for every fit
+int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, const double *qbase, const int *gsel,
+               const double *base, const double *Ls, const double *lo, const double *lambda0, const double *lam0s,
+               const double *betas, const double *x0, double *coef, double *lam, double *cost, double *fun, int *iters,
+               int *flags, double *hist_coef, double *hist_lam, double *hist_fun, double *hist_cost)
+{
+    if (!opt || nb < 1 || ng < 1) { set_error("bdrt_ridge: bad arguments"); return -1; }
+    std::vector<unsigned char> zd((size_t)ng, 0);
+    for (int g = 0; g < ng && g < 31; ++g) zd[g] = (unsigned char)((opt->zero_delta1 >> g) & 1);
+    std::vector<double> fb((size_t)nb, opt->hl_fbeta);
+    return bdrt_ridge_ex(opt, zd.data(), fb.data(), nb, ng, G, qbase, gsel, base, Ls, lo, lambda0, lam0s, betas, x0, coef, lam, cost,
+                         fun, iters, flags, hist_coef, hist_lam, hist_fun, hist_cost);
 }
 
 }  // extern "C"

@@ -48,6 +48,46 @@ __global__ void gram_q_kernel(const double *__restrict__ WA, const double *__res
     q[i] = -s + (L1 ? L1[i] : 0.0);
 }
 
+// ---- batched weighted Gram: ng spectra that share the unweighted A [R x n] and differ in row weights and targets -----------
+// G[g] = (diag(w_g) A)^T (diag(w_g) A) bit for bit as gram_kernel computes it from the host product diag(w_g) @ A: the
+// operand is the rounded product w_gr * A_ri (what numpy's product with a diagonal matrix yields), rows enter the MFMAs in the
+// same groups of four in the same order.  A stays in L2 across the groups; grid (tiles, tiles, ng), block 64
+__global__ __launch_bounds__(64) void gram_batch_kernel(const double *__restrict__ A, const double *__restrict__ w, int nrows,
+                                                        int n, double *__restrict__ G)
+{
+    const int lane = threadIdx.x, col = lane & 15, kq = lane >> 4;
+    const int i0 = blockIdx.x * 16, j0 = blockIdx.y * 16;
+    const int ia = i0 + col, jb = j0 + col;
+    const double *wg = w + (size_t)blockIdx.z * nrows;
+    double *P = G + (size_t)blockIdx.z * n * n;
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int r0 = 0; r0 < nrows; r0 += 4) {
+        const int r = r0 + kq;
+        const double wr = r < nrows ? wg[r] : 0.0;
+        const double a = (r < nrows && ia < n) ? __dmul_rn(wr, A[(size_t)r * n + ia]) : 0.0;
+        const double b = (r < nrows && jb < n) ? __dmul_rn(wr, A[(size_t)r * n + jb]) : 0.0;
+        acc = mfma_f64(a, b, acc);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = i0 + kq + 4 * q, j = j0 + col;
+        if (i < n && j < n) P[(size_t)i * n + j] = acc[q] + 0.0;
+    }
+}
+
+// q[g][i] = -sum_r (w_gr A_ri)(w_gr t_gr) + L1[i]: gram_q_kernel's sequential sum over r on the rounded products;
+// grid (ceil(n / 64), ng), one thread per column
+__global__ void gram_q_batch_kernel(const double *__restrict__ A, const double *__restrict__ w, const double *__restrict__ t,
+                                    int nrows, int n, const double *__restrict__ L1, double *__restrict__ q)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *wg = w + (size_t)blockIdx.y * nrows, *tg = t + (size_t)blockIdx.y * nrows;
+    double s = 0.0;
+    for (int r = 0; r < nrows; ++r) s += __dmul_rn(wg[r], A[(size_t)r * n + i]) * __dmul_rn(wg[r], tg[r]);
+    q[(size_t)blockIdx.y * n + i] = -s + (L1 ? L1[i] : 0.0);
+}
+
 }  // namespace bdrt
 
 using namespace bdrt;
@@ -88,6 +128,40 @@ int bdrt_gram(const double *WA, const double *WZ, int nrows, int n, const double
         GR_HIP(hipMemcpy(q, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     }
 #undef GR_HIP
+    cleanup();
+    return 0;
+}
+
+int bdrt_gram_batch(const double *A, int R, int n, const double *w, const double *t, int ng, const double *L1vec, double *G,
+                    double *q)
+{
+    if (!A || !w || R < 1 || n < 1 || ng < 1 || ng > 65535 || (!G && !q) || (q && !t)) { set_error("bdrt_gram_batch: bad arguments"); return -1; }
+    bind_process_device();
+    const size_t bA = (size_t)R * n * sizeof(double), bw = (size_t)ng * R * sizeof(double), bL1 = (size_t)n * sizeof(double);
+    const size_t bG = G ? (size_t)ng * n * n * sizeof(double) : 0, bq = q ? (size_t)ng * n * sizeof(double) : 0;
+    // one allocation for the whole call: [A | w | t | L1 | G | q]
+    char *dbuf = nullptr;
+    auto cleanup = [&]() { hipFree(dbuf); };
+#define GB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
+    GB_HIP(hipMalloc((void **)&dbuf, bA + 2 * bw + bL1 + bG + bq));
+    double *dA = (double *)dbuf, *dw = (double *)(dbuf + bA), *dt = (double *)(dbuf + bA + bw), *dL1 = (double *)(dbuf + bA + 2 * bw);
+    double *dG = (double *)(dbuf + bA + 2 * bw + bL1), *dq = (double *)(dbuf + bA + 2 * bw + bL1 + bG);
+    GB_HIP(hipMemcpy(dA, A, bA, hipMemcpyHostToDevice));
+    GB_HIP(hipMemcpy(dw, w, bw, hipMemcpyHostToDevice));
+    if (G) {
+        const int tiles = (n + 15) / 16;
+        hipLaunchKernelGGL(gram_batch_kernel, dim3(tiles, tiles, ng), dim3(64), 0, 0, dA, dw, R, n, dG);
+        GB_HIP(hipGetLastError());
+    }
+    if (q) {
+        GB_HIP(hipMemcpy(dt, t, bw, hipMemcpyHostToDevice));
+        if (L1vec) GB_HIP(hipMemcpy(dL1, L1vec, bL1, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(gram_q_batch_kernel, dim3((n + 63) / 64, ng), dim3(64), 0, 0, dA, dw, dt, R, n, L1vec ? dL1 : nullptr, dq);
+        GB_HIP(hipGetLastError());
+    }
+    if (G) GB_HIP(hipMemcpy(G, dG, bG, hipMemcpyDeviceToHost));
+    if (q) GB_HIP(hipMemcpy(q, dq, bq, hipMemcpyDeviceToHost));
+#undef GB_HIP
     cleanup();
     return 0;
 }

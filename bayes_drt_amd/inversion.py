@@ -6,6 +6,7 @@ with `from bayes_drt_amd.inversion import Inverter`.  What runs where:
   * A / L / M matrices          -> GPU (matrices.py -> bdrt_build_A/_L/_M)
   * `fit` MAP / HMC             -> GPU (stan_models.py -> engine.StanModel -> bdrt_optimize / bdrt_sampler_*)
   * `ridge_fit` Gram + QP       -> bdrt_gram (MFMA) + bdrt_qp_box_batch (interior point on the GPU, replaces cvxopt)
+  * `ridge_fit_many`            -> bdrt_gram_batch (all spectra of a grid in one launch) + bdrt_ridge_ex (all fits in one batch)
   * scaling, weights, Stan data dict, prediction algebra: numpy on the host (not hot: microseconds)
 Out of scope (drift fits, MultiDist, fitY/SA, peak fitting, plotting, file loaders) raise
 NotImplementedError instead of silently doing something else.
@@ -338,6 +339,13 @@ class Inverter:
     # ------------------------------------------------------------------ ridge: set-up shared by all solution paths
     def _ridge_setup(self, frequencies, Z, part, penalty, reg_ord, L1_penalty, scale_Z, nonneg, weights, dZ):
         """Matrices of one ridge problem (reference :370-470): augmented A, penalty bases, Gram matrix and q on the GPU."""
+        st = self._ridge_setup_host(frequencies, Z, part, penalty, reg_ord, L1_penalty, scale_Z, nonneg, weights, dZ)
+        st['G'], st['g'] = self._ridge_gram(st, st['W_re'], st['W_im'], st['WT_re'], st['WT_im'])
+        return st
+
+    def _ridge_setup_host(self, frequencies, Z, part, penalty, reg_ord, L1_penalty, scale_Z, nonneg, weights, dZ):
+        """`_ridge_setup` without the Gram matrix: everything a ridge problem needs from the host.  `ridge_fit_many` computes the
+        Gram matrices of all spectra of a grid afterwards, in one launch (`_ridge_gram_many`)."""
         name = list(self.distributions.keys())[0]
         info = self.distributions[name]
         if info['kernel'] != 'DRT' and dZ:
@@ -391,7 +399,6 @@ class Inverter:
                   # the inductance is not fitted -- for any distribution type (:733-734)
                   zero_delta1=bool(self.fit_inductance == False or part == 'real'))
         st['WT_re'], st['WT_im'] = WT_re, WT_im
-        st['G'], st['g'] = self._ridge_gram(st, W_re, W_im, WT_re, WT_im)
         return st
 
     @staticmethod
@@ -409,6 +416,23 @@ class Inverter:
         G = np.empty((n, n)); g = np.empty(n)
         _lib.check(lib.bdrt_gram(ptr(WA), ptr(WT), WA.shape[0], n, None, None, ptr(G), ptr(g)), 'bdrt_gram')
         return G, -g                                   # bdrt_gram returns q = -(WA^T WT)
+
+    @staticmethod
+    def _ridge_gram_many(sts, part):
+        """[(G, g)] of `_ridge_gram(st, st['W_re'], st['W_im'], st['WT_re'], st['WT_im'], part)` for set-ups that share their
+        unweighted A (one grid): ONE launch of bdrt_gram_batch, which weights the rows on the device and reproduces the
+        single-spectrum entry bit for bit."""
+        st0 = sts[0]
+        which = [k for k, p_ in (('re', 'real'), ('im', 'imag')) if part in ('both', p_)]
+        A = np.ascontiguousarray(np.vstack([st0['A_' + k] for k in which]), dtype=np.float64)
+        w = np.ascontiguousarray(np.stack([np.concatenate([np.diagonal(st['W_' + k]) for k in which]) for st in sts]), dtype=np.float64)
+        t = np.ascontiguousarray(np.stack([np.concatenate([getattr(st['target_s'], 'real' if k == 're' else 'imag') for k in which])
+                                           for st in sts]), dtype=np.float64)
+        lib = _lib.require_gpu()
+        ng, (R, n) = len(sts), A.shape
+        G = np.empty((ng, n, n)); g = np.empty((ng, n))
+        _lib.check(lib.bdrt_gram_batch(ptr(A), R, n, ptr(w), ptr(t), ng, None, ptr(G), ptr(g)), 'bdrt_gram_batch')
+        return [(G[i], -g[i]) for i in range(ng)]
 
     @classmethod
     def _unfitted_part_cost(cls, st, coef, W_re=None, W_im=None, T_re=None, T_im=None):
@@ -441,20 +465,45 @@ class Inverter:
         return a, b, lam0, 2 * a
 
     # ------------------------------------------------------------------ ridge: the whole fit on the GPU (bdrt_ridge)
-    def _ridge_solve_device(self, setups, sel, lambdas, hyper_lambda, hl_beta, hl_fbeta, x0, xtol, max_iter):
-        """A batch of ridge fits in ONE launch: fit j uses the data part setups[sel[j]] and lambda_0 = lambdas[j]."""
+    def _ridge_solve_device(self, setups, sel, lambdas, hyper_lambda, hl_beta, hl_fbeta, x0, xtol, max_iter, history=True,
+                            hl_beta_b=None, hl_fbeta_b=None):
+        """A batch of ridge fits on the device: fit j uses the data part setups[sel[j]] and lambda_0 = lambdas[j]; `hl_beta_b` /
+        `hl_fbeta_b`: one hl_beta / hl_fbeta per fit instead of one for all.  One launch of bdrt_ridge_ex unless the batch is
+        large: the work matrices are nb n^2 doubles, so a batch is cut into launches whose share stays under 1 GiB
+        (BDRT_RIDGE_CHUNK=<fits> forces a smaller cut); the fits are independent, the cut changes no number.
+        history=False: no per-iteration record (`history` of every result is None) for callers that never read it."""
+        n, nb = setups[0]['n'], len(sel)
+        chunk = max(1, (2 ** 30 - 1) // (n * n * 8))
+        if os.environ.get('BDRT_RIDGE_CHUNK'):
+            chunk = max(1, min(chunk, int(os.environ['BDRT_RIDGE_CHUNK'])))
+        hb = list(hl_beta_b) if hl_beta_b is not None else [hl_beta] * nb
+        hf = list(hl_fbeta_b) if hl_fbeta_b is not None else [hl_fbeta] * nb
+        x0a = None
+        if x0 is not None:
+            x0a = np.broadcast_to(np.asarray(x0, dtype=np.float64), (nb, n))
+        out = []
+        for j0 in range(0, nb, chunk):
+            j1 = min(nb, j0 + chunk)
+            used, local = np.unique(np.asarray(sel[j0:j1], dtype=np.int64), return_inverse=True)
+            out += self._ridge_launch([setups[g] for g in used], local, lambdas[j0:j1], hyper_lambda, hb[j0:j1], hf[j0:j1],
+                                      None if x0a is None else x0a[j0:j1], xtol, max_iter, history)
+        return out
+
+    def _ridge_launch(self, setups, sel, lambdas, hyper_lambda, hl_beta_b, hl_fbeta_b, x0, xtol, max_iter, history):
+        """One launch of bdrt_ridge_ex (see `_ridge_solve_device`)."""
         lib = _lib.require_gpu()
         st0 = setups[0]
         n, K, off, nb, ng = st0['n'], st0['K'], st0['off'], len(sel), len(setups)
         o = _lib.RidgeOptions()
         o.n, o.K, o.off = n, K, off
         o.penalty = 1 if st0['penalty'] == 'integral' else 0
-        # (bit g of zero_delta1: data part g -- the real-part fits of a cross-validation exclude the inductance from the
-        #  convergence test, the imaginary-part fits do not)
+        # (one flag per data part -- the real-part fits of a cross-validation exclude the inductance from the convergence
+        #  test, the imaginary-part fits do not --, one hl_fbeta per fit)
         o.max_iter, o.hyper_lambda = int(max_iter), int(bool(hyper_lambda))
-        o.zero_delta1 = sum(int(bool(s_['zero_delta1'])) << g for g, s_ in enumerate(setups))
         o.xtol = float(xtol)
-        o.hl_fbeta = float(hl_fbeta) if (hl_fbeta is not None and st0['penalty'] != 'integral') else 0.0
+        zd = np.ascontiguousarray([bool(s_['zero_delta1']) for s_ in setups], dtype=np.uint8)
+        fb = np.ascontiguousarray([float(v) if (v is not None and st0['penalty'] != 'integral') else 0.0 for v in hl_fbeta_b],
+                                  dtype=np.float64)
         for i in range(3):
             o.reg_ord[i] = float(st0['reg_ord'][i])
         G = np.ascontiguousarray(np.stack([s['G'] for s in setups]))
@@ -462,30 +511,32 @@ class Inverter:
         base = np.ascontiguousarray(np.stack(st0['base']))
         Ls = np.ascontiguousarray(np.stack(st0['Ls'])) if st0['Ls'] is not None else None
         lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64))
-        terms = [self._hyper_prior_terms(st0['penalty'], hl_beta, l) for l in lam]
+        terms = [self._hyper_prior_terms(st0['penalty'], hb_, l) for hb_, l in zip(hl_beta_b, lam)]
         lam0s = np.ascontiguousarray(np.stack([t[2] for t in terms]))
         betas = np.ascontiguousarray(np.stack([t[3] for t in terms]))
         gsel = np.ascontiguousarray(np.asarray(sel, dtype=np.int32))
-        x0a = None
-        if x0 is not None:
-            x0a = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (nb, n)))
+        x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
         coef = np.empty((nb, n)); lamv = np.empty((nb, 3, n)); cost = np.empty(nb); fun = np.empty(nb)
         iters = np.zeros(nb, dtype=np.int32); flags = np.zeros(nb, dtype=np.int32)
         mi = int(max_iter)
-        hc = np.zeros((nb, mi, n)); hl = np.zeros((nb, mi, 3, n)); hf = np.zeros((nb, mi)); hk = np.zeros((nb, mi))
-        rc = lib.bdrt_ridge(C.byref(o), nb, ng, ptr(G), ptr(qbase), ptr(gsel), ptr(base), ptr(Ls), ptr(f64(st0['lo'])), ptr(lam),
-                            ptr(lam0s), ptr(betas), ptr(x0a), ptr(coef), ptr(lamv), ptr(cost), ptr(fun), ptr(iters), ptr(flags),
-                            ptr(hc), ptr(hl), ptr(hf), ptr(hk))
-        _lib.check(rc, 'bdrt_ridge')
+        hc = hl = hf = hk = None
+        if history:
+            hc = np.zeros((nb, mi, n)); hl = np.zeros((nb, mi, 3, n)); hf = np.zeros((nb, mi)); hk = np.zeros((nb, mi))
+        rc = lib.bdrt_ridge_ex(C.byref(o), ptr(zd), ptr(fb), nb, ng, ptr(G), ptr(qbase), ptr(gsel), ptr(base), ptr(Ls),
+                               ptr(f64(st0['lo'])), ptr(lam), ptr(lam0s), ptr(betas), ptr(x0a), ptr(coef), ptr(lamv), ptr(cost),
+                               ptr(fun), ptr(iters), ptr(flags), ptr(hc), ptr(hl), ptr(hf), ptr(hk))
+        _lib.check(rc, 'bdrt_ridge_ex')
         out = []
         for j in range(nb):
             if flags[j] & 4:
                 warnings.warn('bdrt_ridge: a QP reached its iteration limit; the last iterate is used')
             sj = setups[sel[j]]
-            hist = [{'lambda_vectors': [hl[j, t, i].copy() for i in range(3)], 'coef': hc[j, t].copy(), 'fun': hf[j, t],
-                     'cost': hk[j, t] + self._unfitted_part_cost(sj, hc[j, t]),
-                     'result': _QPResult({'x': hc[j, t].copy(), 'primal objective': hf[j, t]}),
-                     'dZ_re': np.ones(n)} for t in range(int(iters[j]))]
+            hist = None
+            if history:
+                hist = [{'lambda_vectors': [hl[j, t, i].copy() for i in range(3)], 'coef': hc[j, t].copy(), 'fun': hf[j, t],
+                         'cost': hk[j, t] + self._unfitted_part_cost(sj, hc[j, t]),
+                         'result': _QPResult({'x': hc[j, t].copy(), 'primal objective': hf[j, t]}),
+                         'dZ_re': np.ones(n)} for t in range(int(iters[j]))]
             out.append(dict(coef=coef[j].copy(), lambda_vectors=[lamv[j, i].copy() for i in range(3)],
                             cost=cost[j] + self._unfitted_part_cost(sj, coef[j]),
                             result=_QPResult({'x': coef[j].copy(), 'primal objective': float(fun[j])}), history=hist,
@@ -744,6 +795,177 @@ class Inverter:
         self.cv_result = {'lambda': lambdas.copy(), 'recv': recv, 'imcv': imcv, 'totcv': tot}
         return best
 
+    # ------------------------------------------------------------------ ridge: many spectra, one batch per grid
+    def ridge_fit_many(self, frequencies, Z_list, part='both', penalty='discrete', reg_ord=2, L1_penalty=0, scale_Z=True,
+                       nonneg=True, weights=None, preset=None, hyper_lambda=True, hl_solution='analytic', hl_beta=2.5,
+                       hl_fbeta=None, lambda_0=1e-2, cv_lambdas=np.logspace(-10, 5, 31), hyper_weights=False, hw_beta=2,
+                       hw_wbar=1, xtol=1e-3, max_iter=20, hyper_a=False, alpha_a=2, hl_beta_a=2, hyper_b=False, sb=1,
+                       correct_phase_offset=False, IERange=None, lambda_phz=1, init_phase_offset=False, x0=None, dZ=False,
+                       dZ_power=0.5):
+        """The fits `[copy(self).ridge_fit(frequencies, Z, ...) for Z in Z_list]` -- the loop of the reference's hyper-ridge
+        comparison study (code_EchemActa/comparisons/hyper-ridge/hyper-ridge run fits.ipynb: a Re-Im cross-validation per
+        spectrum, then one hyper-lambda fit per f_beta from the chosen lambda_0) -- as batches: per frequency grid one
+        launch of bdrt_gram_batch per data part for the Gram matrices of all spectra, one bdrt_ridge_ex batch for the
+        2 x len(cv_lambdas) cross-validation fits of every spectrum whose lambda_0 is 'cv', and one more for the final fits.
+        Every fit performs the arithmetic of the separate call; the results are equal to those of the loop bit for bit.
+
+        Arguments as `ridge_fit`.  `frequencies` is one grid for all spectra or a list with one grid per spectrum (spectra
+        are grouped by grid, each grid's matrices are built once); `lambda_0` (entries may be 'cv'), `hl_fbeta` and `hl_beta`
+        take one value or a list with one value per spectrum (so a list is never read as one hl_beta per derivative order);
+        every other argument is one value for all spectra -- a `weights` array applies to every spectrum of its length.  The
+        study's inner loop over f_beta is written by repeating a spectrum in `Z_list` with a list for `hl_fbeta`.
+        The variants of `ridge_fit` that iterate on the host (dZ, hyper_a, hyper_b, hl_solution='lm', correct_phase_offset,
+        hyper_weights, BDRT_HOST_LAMBDA_LOOP) run as a loop of `ridge_fit` calls on the views.
+        Returns a list of Inverter objects in input order (shallow copies of this one, as `fit_many` returns them) that carry
+        what `ridge_fit` leaves behind, `cv_result` included when lambda_0 came from the cross-validation; this instance and
+        its matrix cache are left as they were.  The batch runs on this process's device: it is not sharded over the ranks
+        of a process group."""
+        import copy
+        who = 'ridge_fit_many'
+        if preset is not None:
+            if preset not in ('Ciucci', 'Huang'):
+                raise ValueError('Invalid preset {}. Options are {}'.format(preset, ['Ciucci', 'Huang']))
+            if preset == 'Ciucci':
+                penalty, lambda_0, hl_fbeta = 'discrete', 'cv', 0.1
+            else:
+                penalty, hl_beta, lambda_0, weights = 'integral', 2.5, 1e-2, 'modulus'
+        Z_list = [np.asarray(Z) for Z in Z_list]
+        ns = len(Z_list)
+        lam_s = self._per_spectrum(lambda_0, ns, 'lambda_0', who)
+        fb_s = self._per_spectrum(hl_fbeta, ns, 'hl_fbeta', who)
+        hb_s = self._per_spectrum(hl_beta, ns, 'hl_beta', who)
+        per_grid = isinstance(frequencies, (list, tuple)) and ns > 0 and len(frequencies) == ns and \
+            all(np.ndim(f) == 1 for f in frequencies)
+        if isinstance(frequencies, np.ndarray) and frequencies.ndim == 2:
+            per_grid = True
+            if len(frequencies) != ns:
+                raise ValueError('%s: %d frequency grids for %d spectra' % (who, len(frequencies), ns))
+        freqs = [np.asarray(f, dtype=float) for f in frequencies] if per_grid else [frequencies] * ns
+        # the argument checks of ridge_fit, before anything reaches the GPU
+        if penalty not in ('discrete', 'cholesky', 'integral'):
+            raise ValueError(f'Invalid penalty argument {penalty}. Options are integral, discrete, and cholesky')
+        for hb in hb_s:
+            if penalty == 'integral' and np.min(hb) <= 2:
+                raise ValueError('hl_beta must be greater than 2 for penalty integral')
+            if penalty != 'integral' and np.min(hb) <= 1:
+                raise ValueError('hl_beta must be greater than 1 for penalty cholesky and discrete')
+        if hyper_lambda and hyper_weights:
+            raise ValueError('hyper_lambda and hyper_weights fits cannot be performed simultaneously')
+        if len(self.distributions) > 1:
+            raise ValueError('ridge_fit cannot be used to fit multiple distributions')
+        if correct_phase_offset and IERange is None:
+            raise ValueError('IERange must be provided if correct_phase_offset==True')
+        if hl_solution not in ('analytic', 'lm'):
+            raise ValueError("hl_solution must be 'analytic' or 'lm'")
+        if part not in ('both', 'real', 'imag'):
+            raise ValueError(f"Invalid part {part}. Options are 'both', 'real', or 'imag'")
+        for f, Z in zip(freqs, Z_list):
+            _validate_spectrum(f, Z)
+        if ns == 0:
+            return []
+
+        def is_cv(l):
+            return isinstance(l, str) and l == 'cv'
+
+        def new_view(src):
+            # a copy of the last prepared view of the grid (or of this instance with a matrix cache of its own, as in
+            # `_batch_jobs`) that carries this instance's fit attributes, not those of the view it was copied from
+            inv = copy.copy(src)
+            if src is self:
+                inv.distribution_matrices = {name: dict(st, **({'_penalty': dict(st['_penalty'])} if '_penalty' in st else {}))
+                                             for name, st in self.distribution_matrices.items()}
+            for a in self._RIDGE_SIDE_EFFECTS:
+                if hasattr(self, a):
+                    setattr(inv, a, getattr(self, a))
+                elif hasattr(inv, a):
+                    delattr(inv, a)
+            return inv
+
+        def grid_key(f):
+            return rel_round(np.sort(np.asarray(f, dtype=float))[::-1], 10).tobytes()
+
+        common = dict(part=part, penalty=penalty, reg_ord=reg_ord, L1_penalty=L1_penalty, scale_Z=scale_Z, nonneg=nonneg,
+                      weights=weights, hyper_lambda=hyper_lambda, hl_solution=hl_solution, cv_lambdas=cv_lambdas,
+                      hyper_weights=hyper_weights, hw_beta=hw_beta, hw_wbar=hw_wbar, xtol=xtol, max_iter=max_iter, hyper_a=hyper_a,
+                      alpha_a=alpha_a, hl_beta_a=hl_beta_a, hyper_b=hyper_b, sb=sb, correct_phase_offset=correct_phase_offset,
+                      IERange=IERange, lambda_phz=lambda_phz, init_phase_offset=init_phase_offset, x0=x0, dZ=dZ, dZ_power=dZ_power)
+        views, last_of_grid = [], {}
+        if (dZ or hyper_a or hyper_b or hl_solution != 'analytic' or correct_phase_offset or hyper_weights
+                or os.environ.get('BDRT_HOST_LAMBDA_LOOP')):
+            for i, (f, Z) in enumerate(zip(freqs, Z_list)):
+                key = grid_key(f)
+                inv = new_view(last_of_grid.get(key, self))
+                inv.ridge_fit(f, Z, lambda_0=lam_s[i], hl_fbeta=fb_s[i], hl_beta=hb_s[i], **common)
+                views.append(inv); last_of_grid[key] = inv
+            return views
+        # ---- stage 1: host set-up of every spectrum (for lambda_0 = 'cv': the real-part and imaginary-part problems of the
+        # cross-validation first, as ridge_fit -> ridge_ReImCV set them up), grouped by the exact grid
+        finals, cvs, groups = [], [], {}
+        for i, (f, Z) in enumerate(zip(freqs, Z_list)):
+            key = grid_key(f)
+            inv = new_view(last_of_grid.get(key, self))
+            inv.distribution_fits = {}
+            cv = None
+            if is_cv(lam_s[i]):
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')
+                    cv = [inv._ridge_setup_host(np.asarray(f), Z, p, penalty, reg_ord, L1_penalty, scale_Z, nonneg, weights, dZ)
+                          for p in ('real', 'imag')]
+            st = inv._ridge_setup_host(f, Z, part, penalty, reg_ord, L1_penalty, scale_Z, nonneg, weights, dZ)
+            views.append(inv); finals.append(st); cvs.append(cv); last_of_grid[key] = inv
+            groups.setdefault((key, st['frequencies'].tobytes(), st['n']), []).append(i)
+        lambdas = np.asarray(cv_lambdas, dtype=float)
+        lam_res = list(lam_s)
+        for idx in groups.values():
+            # ---- stage 2: the Gram matrices of the group, one launch per data part (and one for the unfitted part's share of
+            # the reported cost when only one part is fitted)
+            def gram(sts, p_):
+                for st_, (G_, g_) in zip(sts, self._ridge_gram_many(sts, p_)):
+                    st_['G'], st_['g'] = G_, g_
+                if p_ != 'both':
+                    other = 'imag' if p_ == 'real' else 'real'
+                    for st_, Gg in zip(sts, self._ridge_gram_many(sts, other)):
+                        st_[('cost_other', other)] = Gg
+            gram([finals[i] for i in idx], part)
+            icv = [i for i in idx if cvs[i] is not None]
+            if icv:
+                # ---- stage 3: every cross-validation fit of the group in one batch, scored as ridge_ReImCV scores them
+                gram([cvs[i][0] for i in icv], 'real')
+                gram([cvs[i][1] for i in icv], 'imag')
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')
+                    setups = [st_ for i in icv for st_ in cvs[i]]
+                    jobs = [(s_, l_, p_) for s_ in range(len(icv)) for l_ in range(len(lambdas)) for p_ in (0, 1)]
+                    res = views[icv[0]]._ridge_solve_device(
+                        setups, [2 * s_ + p_ for s_, _, p_ in jobs], [lambdas[l_] for _, l_, _ in jobs], hyper_lambda, None, None, x0,
+                        xtol, max_iter, history=False, hl_beta_b=[hb_s[icv[s_]] for s_, _, _ in jobs],
+                        hl_fbeta_b=[fb_s[icv[s_]] for s_, _, _ in jobs])
+                    recv, imcv = np.zeros((len(icv), len(lambdas))), np.zeros((len(icv), len(lambdas)))
+                    for (s_, l_, p_), r in zip(jobs, res):
+                        inv, f, Z = views[icv[s_]], np.asarray(freqs[icv[s_]]), Z_list[icv[s_]]
+                        inv.distribution_fits = {}
+                        inv._ridge_finish(cvs[icv[s_]][p_], r, hyper_lambda, False, max_iter)
+                        Zp = inv.predict_Z(f)
+                        if p_ == 0:
+                            imcv[s_, l_] = np.sum((Z.imag - np.imag(Zp)) ** 2)
+                        else:
+                            recv[s_, l_] = np.sum((Z.real - np.real(Zp)) ** 2)
+                for s_, i in enumerate(icv):
+                    tot = recv[s_] + imcv[s_]
+                    best = lambdas[np.argmin(tot)]
+                    if best == np.min(lambdas) or best == np.max(lambdas):
+                        warnings.warn('Optimal lambda_0 {} determined by Re-Im CV is at the boundary of the evaluated range. Re-run '
+                                      'with an expanded lambda_0 range to obtain an accurate estimate of the optimal lambda_0.'.format(best))
+                    views[i].cv_result = {'lambda': lambdas.copy(), 'recv': recv[s_].copy(), 'imcv': imcv[s_].copy(), 'totcv': tot}
+                    lam_res[i] = best
+            # ---- stage 4: the final fits of the group
+            res = views[idx[0]]._ridge_solve_device([finals[i] for i in idx], list(range(len(idx))), [lam_res[i] for i in idx],
+                                                    hyper_lambda, None, None, x0, xtol, max_iter,
+                                                    hl_beta_b=[hb_s[i] for i in idx], hl_fbeta_b=[fb_s[i] for i in idx])
+            for i, r in zip(idx, res):
+                views[i]._ridge_finish(finals[i], r, hyper_lambda, False, max_iter)
+        return views
+
     # ================================================================== Bayesian fit (reference :1072-1289)
     _RIDGE_SIDE_EFFECTS = ('distribution_fits', 'R_inf', 'inductance', 'fit_type', '_iter_history', 'cv_result', 'error_fit')
 
@@ -885,11 +1107,11 @@ class Inverter:
         return job['batch_key']
 
     @staticmethod
-    def _per_spectrum(value, n, name):
-        """An option of `fit_many` given once (every spectrum) or as a list / array of one value per spectrum."""
+    def _per_spectrum(value, n, name, who='fit_many'):
+        """An option of `fit_many` / `ridge_fit_many` given once (every spectrum) or as a list / array of one value per spectrum."""
         if isinstance(value, (list, tuple, np.ndarray)):
             if len(value) != n:
-                raise ValueError('fit_many: %s has %d entries for %d spectra' % (name, len(value), n))
+                raise ValueError('%s: %s has %d entries for %d spectra' % (who, name, len(value), n))
             return list(value)
         return [value] * n
 

@@ -235,6 +235,14 @@ int bdrt_gram(const double *WA, const double *WZ, int nrows, int n, const double
 /* min 1/2 x^T P x + q^T x  s.t. x >= lo (lo[i] = -inf allowed): primal-dual interior point with cvxopt-like
  * tolerances (abstol 1e-7, reltol 1e-6, feastol 1e-7).  Returns iterations (>=0) or <0. */
 int bdrt_qp_box(const double *P, const double *q, const double *lo, int n, double *x, double *primal_objective);
+/* The Gram matrices of ng spectra that share the unweighted A [R x n] (row-major) and differ in their row weights w [ng][R] and
+ * targets t [ng][R] (Inverter.ridge_fit_many: the weighting schemes depend on Z), in one launch over (tile, tile, group):
+ *   G[g] = sum_r (w_gr A_ri)(w_gr A_rj),  q[g] = -sum_r (w_gr A_ri)(w_gr t_gr) + L1vec     (L1vec [n] or NULL, shared)
+ * G [ng][n][n], q [ng][n]; either may be NULL (t is needed for q only).  The operands are the rounded products w_gr * A_ri, in
+ * the row order and the groups of four rows per MFMA of the single-spectrum entry, so that every group equals
+ * bdrt_gram(diag(w_g) A, diag(w_g) t_g, R, n, NULL, L1vec, ...) bit for bit. */
+int bdrt_gram_batch(const double *A, int R, int n, const double *w, const double *t, int ng, const double *L1vec, double *G,
+                    double *q);
 /* The same solver on the GPU for a batch of nb problems that share n and lo (one workgroup per problem, KKT matrix
  * factored in LDS): P [nb][n][n], q [nb][n], x [nb][n], primal_objective [nb] or NULL, iterations [nb] or NULL.
  * This is what Inverter.ridge_fit / ridge_ReImCV call (reference inversion.py:1043-1067 inside the loops at :560-740 and
@@ -271,15 +279,23 @@ typedef struct {
     int penalty;            /* 0 discrete, 1 integral */
     int max_iter;
     int hyper_lambda;
-    int zero_delta1;        /* bit g: fits with gsel == g leave entry 1 out of the convergence test (ng <= 31) */
+    int zero_delta1;        /* bdrt_ridge only.  bit g: fits with gsel == g leave entry 1 out of the convergence test (g < 31) */
     double xtol;
-    double hl_fbeta;        /* <= 0: analytic discrete update */
+    double hl_fbeta;        /* bdrt_ridge only.  <= 0: analytic discrete update */
     double reg_ord[3];
 } bdrt_ridge_options;
 int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, const double *qbase, const int *gsel,
                const double *base, const double *Ls, const double *lo, const double *lambda0, const double *lam0s,
                const double *betas, const double *x0, double *coef, double *lam, double *cost, double *fun, int *iters,
                int *flags, double *hist_coef, double *hist_lam, double *hist_fun, double *hist_cost);
+/* The same fits with one flag per data part and one hl_fbeta per fit instead of the two option fields (which this entry does not
+ * read): zero_delta1_g [ng] (non-zero: the fits on data part g leave entry 1 out of the convergence test; any ng),
+ * hl_fbeta_b [nb] (<= 0: the analytic update).  bdrt_ridge expands its bit mask and its scalar and calls this entry. */
+int bdrt_ridge_ex(const bdrt_ridge_options *opt, const unsigned char *zero_delta1_g, const double *hl_fbeta_b, int nb, int ng,
+                  const double *G, const double *qbase, const int *gsel, const double *base, const double *Ls, const double *lo,
+                  const double *lambda0, const double *lam0s, const double *betas, const double *x0, double *coef, double *lam,
+                  double *cost, double *fun, int *iters, int *flags, double *hist_coef, double *hist_lam, double *hist_fun,
+                  double *hist_cost);
 
 /* ---- (4) posterior post-processing on the device ------------------------------------
  * Replaces the numpy reductions applied to the HMC draws right after `sampling`:
