@@ -1,0 +1,517 @@
+// bdrt_loo.hip -- PSIS-LOO and WAIC of HMC draws on the device (include/bdrt.h section (4)).
+//
+// Model comparison of sampling fits: leave-one-out cross-validation of the posterior by Pareto-smoothed importance sampling
+// (Vehtari, Gelman, Gabry 2017) and WAIC.  Definitions: tests/psis_numpy.py (the yardstick).  Every observation is a column of S
+// log-likelihoods, one per draw; the draws arrive row-major ([G][S][N]), so columns are strided by N doubles.
+//
+//   loglik_kernel     ll = log normal(z | Z_hat, sigma_tot) per draw and observation, optionally summed over the real and the
+//                     imaginary part of one frequency
+//   transpose_kernel  [G][S][N] -> [G][N][S] through a 32 x 33 LDS tile (256-B rows on both sides, conflict-free column reads)
+//   psis_kernel       one workgroup (8 waves) per column:
+//     1  the column goes to LDS; max, min, log-sum-exp, mean, centred sum of squares        -> lpd, p_waic
+//     2  x = min(ll) - ll (the log ratios -ll shifted by their maximum) replaces the column
+//     3  the (M+1)-th largest x by radix select (8 passes of 8 bits on the order-preserving 64-bit key; histogram in LDS,
+//        equal bins of a wave merged into one atomic); cutoff = max(that, log DBL_MIN)
+//     4  one sweep: values above the cutoff are compacted into the tail buffer (<= ceil(S/5)), the others add their terms to
+//        the two body sums -- after this the column itself is no longer needed
+//     5  bitonic sort of the tail only (same-direction network, any length, no padding stored)
+//     6  y = exp(tail) - exp(cutoff) goes where the column was; Zhang-Stephens fit: one wave per b_j, lanes over y
+//     7  smoothed tail values (stored behind y), the two tail sums; a tail element's ll is min(ll) minus its sorted x
+//        -> elpd_loo, pareto_k, n_tail
+// Every sum is a per-thread strided partial, a wave butterfly and the eight wave partials added in order; the compaction order
+// (the one thing atomics decide) is erased by the sort.  So a column gives the same bits alone or in any batch.  This file is
+// compiled with -ffp-contract=off: every product and sum is rounded separately, as in the numpy statement.
+#include <cfloat>
+#include <cmath>
+
+#include "bdrt_host.h"
+
+namespace bdrt {
+
+constexpr int LO_NT = 512;                       // 8 waves
+constexpr int LO_NW = LO_NT / 64;
+constexpr int LO_MAX_S = 16384;                  // draws per column: 128 KiB column + 26 KiB tail + scratch <= 160 KiB
+constexpr int LO_MAX_M = 96;                     // b_j of the Pareto fit: 30 + sqrt(ceil(16384 / 5)) = 87
+constexpr int LO_TILE = 32;
+
+__global__ __launch_bounds__(256) void loglik_kernel(const double *__restrict__ Zhat, const double *__restrict__ sig,
+                                                     const double *__restrict__ z, size_t rows, int S, int N2, int pair,
+                                                     double c0, double *__restrict__ out)
+{
+    // rows = G * S draw rows; one thread per output element
+    const int No = pair ? N2 / 2 : N2;
+    const size_t total = rows * (size_t)No;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t r = e / No;
+        const int j = (int)(e - r * No);
+        const size_t g = r / S;
+        double acc = 0.0;
+        for (int h = 0; h <= pair; ++h) {
+            const int c = j + h * No;
+            const double s = sig[r * N2 + c];
+            const double q = (z[g * N2 + c] - Zhat[r * N2 + c]) / s;
+            double v = (c0 - log(s)) - 0.5 * (q * q);
+            if (!(s > 0.0) || !isfinite(s)) v = NAN;
+            acc = h ? acc + v : v;
+        }
+        out[e] = acc;
+    }
+}
+
+// in [G][S][N] -> out [G][N][S]
+__global__ __launch_bounds__(256) void transpose_kernel(const double *__restrict__ in, double *__restrict__ out, int S, int N,
+                                                        int tilesS, int tilesN)
+{
+    __shared__ double tile[LO_TILE][LO_TILE + 1];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                  // 32 x 8
+    size_t b = blockIdx.x;
+    const int tn = (int)(b % tilesN); b /= tilesN;
+    const int ts = (int)(b % tilesS);
+    const size_t g = b / tilesS;
+    const double *src = in + g * (size_t)S * N;
+    double *dst = out + g * (size_t)S * N;
+    const int s0 = ts * LO_TILE, n0 = tn * LO_TILE;
+#pragma unroll
+    for (int k = 0; k < LO_TILE; k += 8) {
+        const int s = s0 + ty + k, n = n0 + tx;
+        if (s < S && n < N) tile[ty + k][tx] = src[(size_t)s * N + n];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < LO_TILE; k += 8) {
+        const int n = n0 + ty + k, s = s0 + tx;
+        if (s < S && n < N) dst[(size_t)n * S + s] = tile[tx][ty + k];
+    }
+}
+
+struct LooArgs {
+    const double *T;                             // [columns][S] device
+    const int *M;                                // [columns] tail length
+    int S, cap;                                  // cap = ceil(S / 5): capacity of the tail buffer
+    double log_dbl_min, log_S;
+    double *lpd, *elpd, *khat, *pwaic;           // [columns] device
+    int *ntail;
+};
+
+__device__ inline double lo_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ inline double lo_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// block reductions in a fixed order: wave butterflies, then the eight wave results combined in order by every thread
+__device__ inline double lo_block_sum(double v, double *red)
+{
+    v = lo_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int i = 1; i < LO_NW; ++i) t += red[i];
+    return t;
+}
+
+__device__ inline double lo_block_max(double v, double *red)
+{
+    v = lo_wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int i = 1; i < LO_NW; ++i) t = fmax(t, red[i]);
+    return t;
+}
+
+// order-preserving key of a double (no NaN here): larger value <=> larger key
+__device__ inline unsigned long long lo_key(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ inline double lo_unkey(unsigned long long k)
+{
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)u);
+}
+
+__device__ inline double lo_gpinv(double p, double k, double sigma)
+{
+    if (!(sigma > 0.0)) return NAN;
+    double x;
+    if (fabs(k) < DBL_EPSILON) x = -log1p(-p);
+    else x = expm1(-k * log1p(-p)) / k;
+    return x * sigma;
+}
+
+__global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int S = a.S;
+    const size_t c = blockIdx.x;
+    double *col = lds;                                                // [S]      ll, then x, then y | smoothed tail
+    double *tail = col + S;                                           // [cap]    tail of x, sorted ascending
+    double *red = tail + a.cap;                                       // [LO_NW]
+    double *bj = red + LO_NW;                                         // [LO_MAX_M] each
+    double *kj = bj + LO_MAX_M;
+    double *Lj = kj + LO_MAX_M;
+    double *wj = Lj + LO_MAX_M;
+    double *sc = wj + LO_MAX_M;                                       // [4]
+    int *hist = (int *)(sc + 4);                                      // [256]
+    int *si = hist + 256;                                             // [4]
+    const double *src = a.T + c * (size_t)S;
+
+    // ---- 1: column to LDS; extremes, log-sum-exp, mean and centred sum of squares
+    int bad = 0;
+    double mx = -INFINITY, mn = INFINITY, sum = 0.0;
+    for (int s = tid; s < S; s += LO_NT) {
+        const double v = src[s];
+        bad |= !isfinite(v);
+        col[s] = v;
+        mx = fmax(mx, v);
+        mn = fmin(mn, v);
+        sum += v;
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) {
+        if (tid == 0) { a.lpd[c] = NAN; a.elpd[c] = NAN; a.khat[c] = NAN; a.pwaic[c] = NAN; a.ntail[c] = 0; }
+        return;
+    }
+    mx = lo_block_max(mx, red);
+    mn = -lo_block_max(-mn, red);
+    if (mx == mn) {                                                   // all draws equal: nothing to reweight
+        if (tid == 0) { a.lpd[c] = mx; a.elpd[c] = mx; a.khat[c] = INFINITY; a.pwaic[c] = 0.0; a.ntail[c] = 0; }
+        return;
+    }
+    const double mean = lo_block_sum(sum, red) / (double)S;
+    double se = 0.0, sq = 0.0;
+    for (int s = tid; s < S; s += LO_NT) {
+        const double v = col[s], d = v - mean;
+        se += exp(v - mx);
+        sq = fma(d, d, sq);
+    }
+    se = lo_block_sum(se, red);
+    sq = lo_block_sum(sq, red);
+    if (tid == 0) {
+        a.lpd[c] = (mx + log(se)) - a.log_S;
+        a.pwaic[c] = sq / (double)(S - 1);
+    }
+    // ---- 2: shifted log ratios
+    __syncthreads();
+    for (int s = tid; s < S; s += LO_NT) col[s] = mn - col[s];
+    // ---- 3: radix select of the (M+1)-th largest
+    int rank = a.M[c] + 1;
+    unsigned long long prefix = 0;
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        __syncthreads();
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (int base = 0; base < S; base += LO_NT) {
+            const int s = base + tid;
+            bool act = s < S;
+            const unsigned long long key = act ? lo_key(col[s]) : 0ull;
+            if (pass > 0) act = act && ((key >> (shift + 8)) == prefix);
+            const int bin = (int)((key >> shift) & 255ull);
+            const unsigned long long am = __ballot(act);
+            if (am) {
+                const int first = __ffsll((long long)am) - 1;
+                const int b0 = __shfl(bin, first, 64);
+                const unsigned long long same = __ballot(act && bin == b0);
+                if (act) {
+                    if (bin == b0) {
+                        if (lane == first) atomicAdd(&hist[b0], __popcll(same));
+                    } else {
+                        atomicAdd(&hist[bin], 1);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (w == 0) {
+            const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+            const int own = (h0 + h1) + (h2 + h3);
+            int suf = own;                                            // elements in the bins of lanes >= this one
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_down(suf, o, 64);
+                if (lane + o < 64) suf += t;
+            }
+            const int above = suf - own;
+            if (above < rank && rank <= suf) {                        // exactly one lane
+                int acc = above, sel = 4 * lane + 3, left = rank - acc;
+                if (rank > acc + h3) {
+                    acc += h3; sel = 4 * lane + 2; left = rank - acc;
+                    if (rank > acc + h2) {
+                        acc += h2; sel = 4 * lane + 1; left = rank - acc;
+                        if (rank > acc + h1) { acc += h1; sel = 4 * lane; left = rank - acc; }
+                    }
+                }
+                si[0] = sel; si[1] = left;
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | (unsigned long long)si[0];
+        rank = si[1];
+    }
+    const double cutoff = fmax(lo_unkey(prefix), a.log_dbl_min);
+    const double ecut = exp(cutoff);
+    // ---- 4: compact the tail, sum the body
+    __syncthreads();
+    if (tid == 0) si[2] = 0;
+    __syncthreads();
+    double bden = 0.0, bnum = 0.0;
+    for (int base = 0; base < S; base += LO_NT) {
+        const int s = base + tid;
+        const bool in = s < S;
+        const double x = in ? col[s] : 0.0;
+        const bool up = in && x > cutoff;
+        if (in && !up) {
+            bden += exp(x - cutoff);
+            bnum += exp((x + src[s]) - mn);
+        }
+        const unsigned long long um = __ballot(up);
+        if (um) {
+            const int first = __ffsll((long long)um) - 1;
+            int pos = 0;
+            if (lane == first) pos = atomicAdd(&si[2], __popcll(um));
+            pos = __shfl(pos, first, 64) + __popcll(um & ((1ull << lane) - 1ull));
+            if (up && pos < a.cap) tail[pos] = x;
+        }
+    }
+    bden = lo_block_sum(bden, red);
+    bnum = lo_block_sum(bnum, red);                                   // (its barriers also publish tail[] and si[2])
+    const int n = min(si[2], a.cap);
+    // ---- 5: sort the tail ascending; partners past the end are +inf and never move
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int p = tid; p < (n2 >> 1); p += LO_NT) {
+                int i, q;
+                if (j == (k >> 1)) {
+                    const int blk = p / j, off = p - blk * j;
+                    i = blk * k + off;
+                    q = blk * k + (k - 1 - off);
+                } else {
+                    const int blk = p / j, off = p - blk * j;
+                    i = blk * 2 * j + off;
+                    q = i + j;
+                }
+                if (q < n) {
+                    const double u = tail[i], v = tail[q];
+                    if (u > v) { tail[i] = v; tail[q] = u; }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 6: generalised-Pareto fit to y = exp(tail) - exp(cutoff)
+    double khat = INFINITY, sigma = NAN;
+    double *y = col, *sm = col + a.cap;                               // 2 cap <= S for S >= 4; else n <= 4 and neither is used
+    if (n > 4) {
+        for (int r = tid; r < n; r += LO_NT) y[r] = exp(tail[r]) - ecut;
+        __syncthreads();
+        const int m = min(30 + (int)sqrt((double)n), LO_MAX_M);
+        const double dn = (double)n;
+        if (tid < m) {
+            double b = 1.0 - sqrt((double)m / ((double)(tid + 1) - 0.5));
+            b /= 3.0 * y[(int)(dn / 4.0 + 0.5) - 1];
+            b += 1.0 / y[n - 1];
+            bj[tid] = b;
+        }
+        __syncthreads();
+        for (int j = w; j < m; j += LO_NW) {
+            const double nb = -bj[j];
+            double s = 0.0;
+            for (int r = lane; r < n; r += 64) s += log1p(nb * y[r]);
+            s = lo_wave_sum(s);
+            if (lane == 0) kj[j] = s / dn;
+        }
+        __syncthreads();
+        if (tid < m) Lj[tid] = dn * ((log(-bj[tid] / kj[tid]) - kj[tid]) - 1.0);
+        __syncthreads();
+        if (tid < m) {
+            double s = 0.0;
+            const double L = Lj[tid];
+            for (int i = 0; i < m; ++i) s += exp(Lj[i] - L);
+            wj[tid] = 1.0 / s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double sw = 0.0, bp = 0.0;
+            for (int j = 0; j < m; ++j)
+                if (wj[j] >= 10.0 * DBL_EPSILON) sw += wj[j];
+            for (int j = 0; j < m; ++j)
+                if (wj[j] >= 10.0 * DBL_EPSILON) bp += bj[j] * (wj[j] / sw);
+            sc[0] = bp;
+        }
+        __syncthreads();
+        const double bp = sc[0];
+        double s = 0.0;
+        for (int r = tid; r < n; r += LO_NT) s += log1p(-bp * y[r]);
+        const double km = lo_block_sum(s, red) / dn;
+        sigma = -km / bp;
+        khat = (dn * km + 5.0) / (dn + 10.0);
+    }
+    // ---- 7: smoothed tail, the tail sums, results
+    const bool smooth = n > 4 && isfinite(khat);
+    double mt = -INFINITY, ut = -INFINITY;
+    for (int r = tid; r < n; r += LO_NT) {
+        const double t = tail[r];
+        double v = t;
+        if (smooth) {
+            v = log(lo_gpinv(((double)r + 0.5) / (double)n, khat, sigma) + ecut);
+            if (v > 0.0) v = 0.0;
+            sm[r] = v;
+        }
+        mt = fmax(mt, v);
+        ut = fmax(ut, v + (mn - t));
+    }
+    mt = lo_block_max(mt, red);
+    ut = lo_block_max(ut, red);
+    double tden = 0.0, tnum = 0.0;
+    for (int r = tid; r < n; r += LO_NT) {
+        const double t = tail[r];
+        const double v = smooth ? sm[r] : t;
+        tden += exp(v - mt);
+        tnum += exp((v + (mn - t)) - ut);
+    }
+    tden = lo_block_sum(tden, red);
+    tnum = lo_block_sum(tnum, red);
+    if (tid == 0) {
+        double lden, lnum;
+        if (n == 0) {
+            lden = cutoff + log(bden);
+            lnum = mn + log(bnum);
+        } else {
+            const double md = fmax(cutoff, mt), mu = fmax(mn, ut);
+            lden = md + log(bden * exp(cutoff - md) + tden * exp(mt - md));
+            lnum = mu + log(bnum * exp(mn - mu) + tnum * exp(ut - mu));
+        }
+        a.elpd[c] = lnum - lden;
+        a.khat[c] = khat;
+        a.ntail[c] = n;
+    }
+}
+
+static size_t loo_lds_bytes(int S, int cap)
+{
+    return ((size_t)S + cap + LO_NW + 4 * LO_MAX_M + 4) * sizeof(double) + (256 + 4) * sizeof(int);
+}
+
+// tail length M = ceil(min(S / 5, 3 sqrt(S / reff))), as the numpy statement computes it (host arithmetic)
+static int loo_tail_lengths(int S, size_t ncol, const double *reff, std::vector<int> &M)
+{
+    M.resize(ncol);
+    const int cap = (S + 4) / 5;
+    for (size_t i = 0; i < ncol; ++i) {
+        const double r = reff ? reff[i] : 1.0;
+        if (!(r > 0.0) || !std::isfinite(r)) { set_error("bdrt_psis_loo: reff[%zu] = %g is not a positive number", i, r); return -1; }
+        const double v = std::ceil(std::min((double)S / 5.0, 3.0 * std::sqrt((double)S / r)));
+        M[i] = std::max(1, std::min(cap, (int)v));
+    }
+    return 0;
+}
+
+}  // namespace bdrt
+
+using namespace bdrt;
+
+extern "C" {
+
+int bdrt_pointwise_loglik(const double *Zhat, const double *sig, const double *z, int G, int S, int N2, int pair,
+                          double *ll_out)
+{
+    if (!Zhat || !sig || !z || !ll_out || G < 1 || S < 1 || N2 < 1 || (pair != 0 && pair != 1) || (pair && (N2 & 1))) {
+        set_error("bdrt_pointwise_loglik: bad arguments");
+        return -1;
+    }
+    bind_process_device();
+    const size_t rows = (size_t)G * S, nin = rows * N2, nout = rows * (pair ? N2 / 2 : N2);
+    double *dZh = nullptr, *dSg = nullptr, *dz = nullptr, *dOut = nullptr;
+    auto cleanup = [&]() { hipFree(dZh); hipFree(dSg); hipFree(dz); hipFree(dOut); };
+#define LL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("bdrt_pointwise_loglik: %s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
+    LL_HIP(hipMalloc((void **)&dZh, nin * sizeof(double)));
+    LL_HIP(hipMalloc((void **)&dSg, nin * sizeof(double)));
+    LL_HIP(hipMalloc((void **)&dz, (size_t)G * N2 * sizeof(double)));
+    LL_HIP(hipMalloc((void **)&dOut, nout * sizeof(double)));
+    LL_HIP(hipMemcpy(dZh, Zhat, nin * sizeof(double), hipMemcpyHostToDevice));
+    LL_HIP(hipMemcpy(dSg, sig, nin * sizeof(double), hipMemcpyHostToDevice));
+    LL_HIP(hipMemcpy(dz, z, (size_t)G * N2 * sizeof(double), hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)std::min<size_t>((nout + 255) / 256, 1u << 20);
+    hipLaunchKernelGGL(loglik_kernel, dim3(blocks), dim3(256), 0, nullptr, dZh, dSg, dz, rows, S, N2, pair,
+                       -0.5 * std::log(2.0 * M_PI), dOut);
+    LL_HIP(hipGetLastError());
+    LL_HIP(hipDeviceSynchronize());
+    LL_HIP(hipMemcpy(ll_out, dOut, nout * sizeof(double), hipMemcpyDeviceToHost));
+#undef LL_HIP
+    cleanup();
+    return 0;
+}
+
+int bdrt_psis_loo_max_draws(void) { return LO_MAX_S; }
+
+int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, double *lpd, double *elpd_loo, double *pareto_k,
+                  double *p_waic, int *n_tail)
+{
+    if (!ll || !lpd || !elpd_loo || !pareto_k || !p_waic || !n_tail || G < 1 || S < 2 || N < 1) {
+        set_error("bdrt_psis_loo: bad arguments");
+        return -1;
+    }
+    if (S > LO_MAX_S) { set_error("bdrt_psis_loo: %d draws per column, the kernel holds at most %d", S, LO_MAX_S); return -2; }
+    const size_t ncol = (size_t)G * N;
+    if (ncol > 0x7fffffffull) { set_error("bdrt_psis_loo: too many columns"); return -2; }
+    std::vector<int> M;
+    if (loo_tail_lengths(S, ncol, reff, M)) return -1;
+    bind_process_device();
+    const int cap = (S + 4) / 5;
+    const size_t lds = loo_lds_bytes(S, cap), nel = ncol * S;
+    double *dIn = nullptr, *dT = nullptr, *dOut = nullptr;
+    int *dM = nullptr;
+    auto cleanup = [&]() { hipFree(dIn); hipFree(dT); hipFree(dOut); hipFree(dM); };
+#define LO_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("bdrt_psis_loo: %s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
+    LO_HIP(hipMalloc((void **)&dIn, nel * sizeof(double)));
+    LO_HIP(hipMalloc((void **)&dT, nel * sizeof(double)));
+    LO_HIP(hipMalloc((void **)&dOut, 4 * ncol * sizeof(double)));
+    LO_HIP(hipMalloc((void **)&dM, 2 * ncol * sizeof(int)));
+    LO_HIP(hipMemcpy(dIn, ll, nel * sizeof(double), hipMemcpyHostToDevice));
+    LO_HIP(hipMemcpy(dM, M.data(), ncol * sizeof(int), hipMemcpyHostToDevice));
+    const int tilesS = (S + LO_TILE - 1) / LO_TILE, tilesN = (N + LO_TILE - 1) / LO_TILE;
+    const size_t tiles = (size_t)G * tilesS * tilesN;
+    if (tiles > 0x7fffffffull) { set_error("bdrt_psis_loo: too many tiles"); cleanup(); return -2; }
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, dIn, dT, S, N, tilesS, tilesN);
+    LO_HIP(hipGetLastError());
+    static LdsAttrCache cache;
+    LO_HIP(cache.ensure(lds, [&]() {
+        return hipFuncSetAttribute((const void *)psis_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }));
+    LooArgs a;
+    a.T = dT; a.M = dM; a.S = S; a.cap = cap;
+    a.log_dbl_min = std::log(DBL_MIN); a.log_S = std::log((double)S);
+    a.lpd = dOut; a.elpd = dOut + ncol; a.khat = dOut + 2 * ncol; a.pwaic = dOut + 3 * ncol;
+    a.ntail = dM + ncol;
+    hipLaunchKernelGGL(psis_kernel, dim3((unsigned)ncol), dim3(LO_NT), lds, nullptr, a);
+    LO_HIP(hipGetLastError());
+    LO_HIP(hipDeviceSynchronize());
+    double *outs[4] = {lpd, elpd_loo, pareto_k, p_waic};
+    for (int k = 0; k < 4; ++k) LO_HIP(hipMemcpy(outs[k], dOut + k * ncol, ncol * sizeof(double), hipMemcpyDeviceToHost));
+    LO_HIP(hipMemcpy(n_tail, dM + ncol, ncol * sizeof(int), hipMemcpyDeviceToHost));
+#undef LO_HIP
+    cleanup();
+    return 0;
+}
+
+}  // extern "C"

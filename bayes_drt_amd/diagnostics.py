@@ -12,6 +12,9 @@ parameters of its parallel blocks (Y_hat*, Z_hat_p*, x_sum*) and its generated q
 (`SavedFit`) has the arrays it stored, plus Z_hat_re / Z_hat_im / dups, which follow from them (not q: that needs the
 differentiation matrices).
 
+Comparing fits (PSIS-LOO, WAIC, the Pareto k-hat of every observation) is in bayes_drt_amd.loo; its relative efficiency
+comes from `column_diagnostics` here.
+
 Out of scope: pystan's E-BFMI check ('energy').  It needs the Hamiltonian of every draw, and no sampler kernel records it;
 `checks=['energy']` raises NotImplementedError.
 """

@@ -7,6 +7,7 @@ with `from bayes_drt_amd.inversion import Inverter`.  What runs where:
   * `fit` MAP / HMC             -> GPU (stan_models.py -> engine.StanModel -> bdrt_optimize / bdrt_sampler_*)
   * `ridge_fit` Gram + QP       -> bdrt_gram (MFMA) + bdrt_qp_box_batch (interior point on the GPU, replaces cvxopt)
   * `ridge_fit_many`            -> bdrt_gram_batch (all spectra of a grid in one launch) + bdrt_ridge_ex (all fits in one batch)
+  * `loo` / `loo_many`           -> bdrt_pointwise_loglik + bdrt_psis_loo (PSIS-LOO and WAIC of sampling fits, loo.py)
   * scaling, weights, Stan data dict, prediction algebra: numpy on the host (not hot: microseconds)
 Out of scope (drift fits, MultiDist, fitY/SA, peak fitting, plotting, file loaders) raise
 NotImplementedError instead of silently doing something else.
@@ -1756,6 +1757,56 @@ class Inverter:
             raise ValueError('Percentile prediction is only available for bayes_fit')
         coef = post.percentile(self._sample_result[self._get_stan_coef_name(distribution_name)], percentile, axis=0)
         return self._rescale_coef(coef, self.distributions[distribution_name]['dist_type'])
+
+    # ================================================================== model comparison (bayes_drt_amd.loo)
+    def _loo_job(self, part):
+        """(fit, scaled data [2 Nf], columns, frequencies) of this instance's sampling fit for `loo`."""
+        if self.fit_type != 'bayes':
+            raise ValueError('LOO model comparison is only available for bayes_fit')
+        if part not in ('both', 'real', 'imag'):
+            raise ValueError("part must be 'both', 'real' or 'imag'")
+        dat = getattr(self, '_stan_input', None)
+        if dat is not None and 'Z' in dat:
+            z = np.asarray(dat['Z'], dtype=float).reshape(-1)
+        else:
+            Zs = np.asarray(self.Z_train) / self._Z_scale
+            z = np.concatenate((Zs.real, Zs.imag))
+        nf = len(z) // 2
+        columns = None if part == 'both' else (slice(0, nf) if part == 'real' else slice(nf, 2 * nf))
+        freq = dat['freq'] if dat is not None and 'freq' in dat else self.f_train
+        return self._sample_result, z, columns, np.asarray(freq, dtype=float)
+
+    def loo(self, unit='frequency', part='both', reff='auto'):
+        """PSIS-LOO and WAIC of this instance's sampling fit (bayes_drt_amd.loo.loo): the expected log pointwise predictive
+        density by leave-one-out cross-validation of the posterior, for ranking fits of ONE spectrum (`loo.compare`) -- other
+        models, nonneg, the outlier error model, basis widths --, and the Pareto shape k-hat per observation, which says which
+        frequencies the posterior hinges on.  unit: 'frequency' (real plus imaginary part of a frequency is one observation) or
+        'point'; part: 'real' / 'imag' for a fit of that part alone (only that half's observations count); reff: 'auto' (MCMC
+        relative efficiency from the fit's chains), None, a number or one per observation.  The log density is that of the
+        impedance as it was supplied (not the scaled one), so fits that scaled the spectrum differently stay comparable.
+        Stores the result as `loo_result` and returns it."""
+        from . import loo as _loo
+        fit, z, columns, freq = self._loo_job(part)
+        self.loo_result = _loo.loo(fit, z, unit=unit, reff=reff, log_scale=float(np.log(self._Z_scale)), columns=columns,
+                                   frequencies=freq)
+        return self.loo_result
+
+    @staticmethod
+    def loo_many(inverters, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+        """`loo()` of every Inverter of a list (what `fit_many` returns): fits of equal size share one launch of each kernel
+        per chunk of at most `chunk_bytes` of host arrays (default bayes_drt_amd.loo.CHUNK_BYTES).  Returns the results in
+        input order, each bit for bit what the Inverter's own `loo()` gives, and stores each as `loo_result`."""
+        from . import loo as _loo
+        jobs = [inv._loo_job(part) for inv in inverters]
+        if len({None if j[2] is None else (j[2].start, j[2].stop) for j in jobs}) > 1:
+            raise ValueError('loo_many: the spectra do not have the same number of frequencies')
+        res = _loo.loo_many([j[0] for j in jobs], [j[1] for j in jobs], unit=unit, reff=reff,
+                            log_scales=[float(np.log(inv._Z_scale)) for inv in inverters],
+                            columns=jobs[0][2] if jobs else None, frequencies=[j[3] for j in jobs],
+                            chunk_bytes=chunk_bytes or _loo.CHUNK_BYTES)
+        for inv, r in zip(inverters, res):
+            inv.loo_result = r
+        return res
 
     # ================================================================== prediction (reference :2571-3311)
     def _get_prediction_matrices(self, frequencies, distributions):

@@ -1,0 +1,230 @@
+"""Model comparison of sampling fits: PSIS-LOO and WAIC (`loo`, `compare`), reduced on the GPU.
+
+Stan users rank fits of one data set by the expected log pointwise predictive density, estimated by leave-one-out
+cross-validation of the posterior with Pareto-smoothed importance sampling (Vehtari, Gelman, Gabry 2017), and by WAIC.  Every
+model text ends in `Z ~ normal(Z_hat, sigma_tot)`, so the pointwise log-likelihood of a draw follows from `fit['Z_hat']` and
+`fit['sigma_tot']`.  The reductions run in bdrt_loo.hip (`bdrt_pointwise_loglik`, `bdrt_psis_loo`: one workgroup per
+observation); the definitions are written out in tests/psis_numpy.py.  Messages go to logging.getLogger('bayes_drt_amd').
+
+Units: an observation is one frequency (`unit='frequency'`: real plus imaginary part, the default) or one scalar
+(`unit='point'`).  The Pareto shape k-hat of an observation says how much the posterior hinges on it: above 0.7 the
+importance-sampling estimate for that observation is unreliable (and the observation is influential).
+
+Out of scope: K-fold or exact refits and moment matching for high-k observations; LOO of MAP or ridge fits.
+"""
+import logging
+
+import numpy as np
+
+from . import _lib
+
+logger = logging.getLogger('bayes_drt_amd')
+
+K_THRESHOLD = 0.7
+UNITS = ('frequency', 'point')
+CHUNK_BYTES = 1 << 30                                # loo_many: host bytes of one chunk's stacked arrays
+
+
+class LooResult(dict):
+    """Result of `loo`: a dict whose entries also read as attributes."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def max_draws():
+    """Largest number of draws per observation the kernel holds."""
+    return int(_lib.load_library().bdrt_psis_loo_max_draws())
+
+
+def _pair(unit):
+    if unit not in UNITS:
+        raise ValueError("unit must be 'frequency' or 'point', not %r" % (unit,))
+    return 1 if unit == 'frequency' else 0
+
+
+# ---------------------------------------------------------------------------------------------------- device reductions
+def pointwise_log_lik(Zhat, sig, z, unit='frequency'):
+    """Log-likelihood of `Z ~ normal(Z_hat, sigma_tot)` per draw and observation on the GPU: Zhat, sig [G, S, 2 Nf] and z
+    [G, 2 Nf] (or [S, 2 Nf] and [2 Nf]: G = 1) -> [G, S, Nf] (unit='frequency': real plus imaginary part) or [G, S, 2 Nf]
+    (unit='point').  A non-positive or non-finite sig gives NaN."""
+    pair = _pair(unit)
+    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
+    one = Zhat.ndim == 2
+    if one:
+        Zhat, sig, z = Zhat[None], sig[None], z[None]
+    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
+        raise ValueError('pointwise_log_lik: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+    G, S, N2 = Zhat.shape
+    if pair and N2 % 2:
+        raise ValueError("pointwise_log_lik: unit='frequency' needs an even number of columns, not %d" % N2)
+    lib = _lib.require_gpu()
+    out = np.empty((G, S, N2 // 2 if pair else N2))
+    _lib.check(lib.bdrt_pointwise_loglik(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, _lib.ptr(out)),
+               'bdrt_pointwise_loglik')
+    return out[0] if one else out
+
+
+def psis_loo(ll, reff=None):
+    """PSIS-LOO and WAIC per column of ll [G, S, N] (or [S, N]: G = 1) on the GPU.  reff: None (1), a number, or [G, N].
+    Returns a dict of lpd, elpd_loo, p_loo, pareto_k, p_waic, elpd_waic (float) and n_tail (int), each [G, N] ([N])."""
+    ll = _lib.f64(ll)
+    one = ll.ndim == 2
+    if one:
+        ll = ll[None]
+    if ll.ndim != 3:
+        raise ValueError('psis_loo: ll must be [S, N] or [G, S, N]')
+    G, S, N = ll.shape
+    if S > max_draws():
+        raise ValueError('psis_loo: %d draws per observation, the kernel holds at most %d' % (S, max_draws()))
+    if S < 2:
+        raise ValueError('psis_loo: at least 2 draws are needed')
+    r = None
+    if reff is not None:
+        r = _lib.f64(np.broadcast_to(np.asarray(reff, dtype=float), (G, N)))
+        if not np.all(np.isfinite(r) & (r > 0)):
+            raise ValueError('psis_loo: reff must be positive and finite')
+    lib = _lib.require_gpu()
+    outs = [np.empty((G, N)) for _ in range(4)]
+    n_tail = np.empty((G, N), dtype=np.int32)
+    _lib.check(lib.bdrt_psis_loo(_lib.ptr(ll), G, S, N, _lib.ptr(r), *[_lib.ptr(o) for o in outs], _lib.ptr(n_tail)),
+               'bdrt_psis_loo')
+    lpd, elpd, k, pw = [o[0] for o in outs] if one else outs
+    return {'lpd': lpd, 'elpd_loo': elpd, 'p_loo': lpd - elpd, 'pareto_k': k, 'p_waic': pw, 'elpd_waic': lpd - pw,
+            'n_tail': n_tail[0] if one else n_tail}
+
+
+def relative_efficiency(ll, chains):
+    """MCMC relative efficiency of the likelihood draws, n_eff(exp(ll - max ll)) / S per column (`column_diagnostics`), for the
+    tail length of PSIS.  ll [S, N] or [G, S, N]; a column without a finite n_eff (constant, or too few draws) gets 1."""
+    from .diagnostics import column_diagnostics
+    ll = np.asarray(ll, dtype=float)
+    S = ll.shape[-2]
+    with np.errstate(invalid='ignore', over='ignore'):
+        lik = np.exp(ll - ll.max(axis=-2, keepdims=True))
+    n_eff = column_diagnostics(lik, chains)[2]
+    r = n_eff / S
+    return np.where(np.isfinite(r) & (r > 0), r, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------- fits
+def _fit_arrays(fit, z, columns):
+    Zhat, sig = np.asarray(fit['Z_hat'], dtype=float), np.asarray(fit['sigma_tot'], dtype=float)
+    z = np.asarray(z, dtype=float).reshape(-1)
+    if Zhat.ndim != 2 or sig.shape != Zhat.shape or z.shape[0] != Zhat.shape[1]:
+        raise ValueError('loo: Z_hat %s, sigma_tot %s and the data %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+    if columns is not None:
+        Zhat, sig, z = Zhat[:, columns], sig[:, columns], z[columns]
+    return np.ascontiguousarray(Zhat), np.ascontiguousarray(sig), np.ascontiguousarray(z)
+
+
+def _reff_arg(reff, ll, chains):
+    if isinstance(reff, str):
+        if reff != 'auto':
+            raise ValueError("reff must be 'auto', None, a number or an array")
+        return relative_efficiency(ll, chains)
+    return reff
+
+
+def _result(p, n_scalar_per_unit, S, log_scale, frequencies=None, prefix=''):
+    """Pointwise kernel outputs of one fit -> LooResult; logs the k-hat line."""
+    shift = n_scalar_per_unit * float(log_scale)
+    n = len(p['lpd'])
+    elpd_i, lpd_i = p['elpd_loo'] - shift, p['lpd'] - shift
+    waic_i = lpd_i - p['p_waic']
+    with np.errstate(invalid='ignore'):
+        bad = np.nonzero(p['pareto_k'] > K_THRESHOLD)[0]
+    res = LooResult(
+        elpd_loo=float(np.sum(p['elpd_loo']) - n * n_scalar_per_unit * float(log_scale)),
+        se=float(np.sqrt(n * np.var(elpd_i))), p_loo=float(np.sum(p['p_loo'])),
+        elpd_waic=float(np.sum(p['elpd_waic']) - n * n_scalar_per_unit * float(log_scale)),
+        p_waic=float(np.sum(p['p_waic'])), se_waic=float(np.sqrt(n * np.var(waic_i))),
+        n_units=n, n_draws=int(S), elpd_i=elpd_i, lpd_i=lpd_i, pareto_k=p['pareto_k'], p_waic_i=p['p_waic'],
+        n_tail=p['n_tail'], n_bad_k=int(len(bad)))
+    if len(bad):
+        where = ''
+        if frequencies is not None and len(frequencies) in (n, n // 2) and len(frequencies):
+            where = ', f = %s Hz' % np.array2string(np.asarray(frequencies, dtype=float)[bad % len(frequencies)], precision=4)
+        logger.warning('%s%d of %d observations have Pareto k > %.1f (indices %s%s): their LOO estimates are unreliable and the '
+                       'posterior hinges on them', prefix, len(bad), n, K_THRESHOLD, bad.tolist(), where)
+    else:
+        logger.info('%sAll Pareto k estimates are below %.1f (largest %.3g)', prefix, K_THRESHOLD,
+                    float(np.nanmax(p['pareto_k'][np.isfinite(p['pareto_k'])], initial=-np.inf)))
+    return res
+
+
+def loo(fit, z, chains=None, unit='frequency', reff='auto', log_scale=0.0, columns=None, frequencies=None):
+    """PSIS-LOO and WAIC of a sampling fit (`StanFit` or `SavedFit`) against the data z [2 Nf] it was fitted to (the Stan data
+    entry 'Z': real parts, then imaginary parts, on the fit's scale).
+
+    chains: chains of the fit (default fit.chains), for reff='auto'.  reff: 'auto' (`relative_efficiency`), None (1), a
+    number or one per observation.  log_scale: subtracted once per scalar observation -- with log(Z scale) the result is a
+    log density of the impedance as supplied, comparable between fits scaled differently.  columns: the scalar observations
+    that count (a slice or index array into the 2 Nf; then every one of them is a unit of its own).
+    Returns a `LooResult`: elpd_loo, se, p_loo, elpd_waic, p_waic, se_waic, n_units, n_draws, the pointwise arrays elpd_i,
+    lpd_i, pareto_k, p_waic_i, n_tail, and n_bad_k, the number of observations with k > 0.7."""
+    pair = _pair(unit) if columns is None else 0
+    Zhat, sig, z = _fit_arrays(fit, z, columns)
+    ll = pointwise_log_lik(Zhat, sig, z, 'frequency' if pair else 'point')
+    chains = int(chains if chains is not None else getattr(fit, 'chains', 1))
+    p = psis_loo(ll, _reff_arg(reff, ll, chains))
+    return _result(p, 2 if pair else 1, ll.shape[0], log_scale, frequencies)
+
+
+def loo_many(fits, zs, chains=None, unit='frequency', reff='auto', log_scales=None, columns=None, frequencies=None,
+             chunk_bytes=CHUNK_BYTES):
+    """`loo` of many fits: fits with equal (draws, observations) go through one launch of each kernel per chunk, a chunk being
+    as many fits as keep its stacked host arrays (Z_hat, sigma_tot, ll) below `chunk_bytes`.  Results in input order, each
+    equal to the single-fit `loo` bit for bit (a column's result does not depend on what else is in the launch)."""
+    n = len(fits)
+    log_scales = [0.0] * n if log_scales is None else list(log_scales)
+    frequencies = [None] * n if frequencies is None else list(frequencies)
+    pair = _pair(unit) if columns is None else 0
+    arrays = [_fit_arrays(f, z, columns) for f, z in zip(fits, zs)]
+    ch = [int(chains if chains is not None else getattr(f, 'chains', 1)) for f in fits]
+    groups = {}
+    for i, a in enumerate(arrays):
+        groups.setdefault((a[0].shape, ch[i]), []).append(i)
+    out = [None] * n
+    for (shape, m), idx in groups.items():
+        per_fit = 3 * shape[0] * shape[1] * 8
+        step = max(1, int(chunk_bytes // per_fit))
+        for k0 in range(0, len(idx), step):
+            sel = idx[k0:k0 + step]
+            Zh, sg, zz = [np.stack([arrays[i][j] for i in sel]) for j in range(3)]
+            ll = pointwise_log_lik(Zh, sg, zz, 'frequency' if pair else 'point')
+            r = _reff_arg(reff, ll, m)
+            if r is not None and np.ndim(r) == 1:
+                r = np.broadcast_to(r, (ll.shape[2],))[None].repeat(len(sel), 0)
+            p = psis_loo(ll, r)
+            for g, i in enumerate(sel):
+                out[i] = _result({k: v[g] for k, v in p.items()}, 2 if pair else 1, shape[0], log_scales[i], frequencies[i],
+                                 'fit %d: ' % i)
+    return out
+
+
+def compare(results):
+    """Rank fits of ONE data set: {name: LooResult} -> list of rows (dicts: name, elpd_loo, se, elpd_diff, dse, p_loo, n_bad_k),
+    best first.  elpd_diff is the difference to the best fit and dse the standard error of the pointwise differences,
+    sqrt(n var(elpd_i - elpd_i of the best)).  Raises ValueError when the results do not cover the same number of units."""
+    if not results:
+        return []
+    names = list(results)
+    n = {int(results[k]['n_units']) for k in names}
+    if len(n) != 1:
+        raise ValueError('compare: the results cover different numbers of observations (%s): not fits of one data set with '
+                         'one unit' % sorted(n))
+    n = n.pop()
+    order = sorted(names, key=lambda k: -float(results[k]['elpd_loo']))
+    best = results[order[0]]
+    rows = []
+    for k in order:
+        r = results[k]
+        d = np.asarray(r['elpd_i']) - np.asarray(best['elpd_i'])
+        rows.append({'name': k, 'elpd_loo': float(r['elpd_loo']), 'se': float(r['se']),
+                     'elpd_diff': float(r['elpd_loo']) - float(best['elpd_loo']), 'dse': float(np.sqrt(n * np.var(d))),
+                     'p_loo': float(r['p_loo']), 'n_bad_k': int(r['n_bad_k'])})
+    return rows

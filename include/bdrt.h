@@ -337,6 +337,21 @@ int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
  * is_pos[C] flags the exp() columns (NULL: none); outputs [G x C].  M <= 64. */
 int bdrt_diagnostics(const double *X, int G, int M, int N, int C, long ldx, const unsigned char *is_pos, double *mean,
                      double *sd, double *n_eff, double *rhat);
+/* Model comparison of sampling fits: PSIS-LOO (Vehtari, Gelman, Gabry 2017) and WAIC; definitions: tests/psis_numpy.py.
+ * Pointwise log-likelihood of `Z ~ normal(Z_hat, sigma_tot)`: Zhat, sig [G][S][N2] and z [G][N2] on the host (G fits, S draws,
+ * N2 = 2 Nf scalar observations).  pair = 0: ll_out [G][S][N2]; pair = 1: ll_out [G][S][N2 / 2], column i = columns i and
+ * i + N2 / 2 added (real and imaginary part of one frequency).  A non-positive or non-finite sig gives NaN. */
+int bdrt_pointwise_loglik(const double *Zhat, const double *sig, const double *z, int G, int S, int N2, int pair,
+                          double *ll_out);
+/* Per column of ll [G][S][N] (host; a column = the S log-likelihoods of one observation): lpd = log mean exp(ll), elpd_loo
+ * with Pareto-smoothed importance weights, the Pareto shape pareto_k of the weights' tail (inf when at most 4 ratios lie
+ * above the cutoff: raw weights), p_waic = var(ll) (ddof = 1) and n_tail, the number of smoothed ratios; outputs [G][N].
+ * reff [G][N]: relative efficiency of each column's draws (NULL: 1); tail length M = ceil(min(S / 5, 3 sqrt(S / reff))).
+ * A column with a non-finite value gives NaN (n_tail 0), that column only.  2 <= S <= bdrt_psis_loo_max_draws() (-2 above).
+ * Bit-reproducible, and a column's results do not depend on what else is in the launch. */
+int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, double *lpd, double *elpd_loo, double *pareto_k,
+                  double *p_waic, int *n_tail);
+int bdrt_psis_loo_max_draws(void);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
