@@ -55,6 +55,22 @@ struct LdsAttrCache {
     }
 };
 
+// move-only owner of one device allocation of n elements of T: hipFree on destruction, unless released
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t n) { reset(); return hipMalloc((void **)&p, n * sizeof(T)); }
+    void reset() { if (p) hipFree(p); p = nullptr; }
+    T *release() { T *q = p; p = nullptr; return q; }
+    operator T *() const { return p; }
+};
+
 struct Problem {
     DevProblem dev;                 // device view (pointers are device pointers), host copy
     DevProblem *d_dev = nullptr;    // the same struct in HBM: kernels take it by pointer (uniform scalar loads)

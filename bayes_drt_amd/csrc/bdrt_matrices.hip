@@ -179,13 +179,6 @@ __global__ void build_M_kernel(const double *tau, int k, double eps, double c0, 
     out[i] = v;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    int alloc(size_t bytes) { BDRT_HIP(hipMalloc(&p, bytes ? bytes : 8)); return 0; }
-    template <class T> T *as() { return (T *)p; }
-};
-
 }  // namespace bdrt
 
 using namespace bdrt;
@@ -211,28 +204,27 @@ int bdrt_build_A_basis(const double *freq, int nf, const double *tau, int k, dou
         return -1;
     }
     bind_process_device();
-    DevBuf dF, dT, dV, dO;
-    int rc;
-    if ((rc = dF.alloc(nf * sizeof(double))) || (rc = dT.alloc(k * sizeof(double)))) return rc;
+    DevBuf<double> dF, dT, dV, dO;
+    BDRT_HIP(dF.alloc(nf)); BDRT_HIP(dT.alloc(k));
     const int nent = toeplitz ? nf + k : nf * k;
-    if ((rc = dV.alloc((size_t)nent * sizeof(double))) || (rc = dO.alloc((size_t)nf * k * sizeof(double)))) return rc;
+    BDRT_HIP(dV.alloc((size_t)nent)); BDRT_HIP(dO.alloc((size_t)nf * k));
     BDRT_HIP(hipMemcpy(dF.p, freq, nf * sizeof(double), hipMemcpyHostToDevice));
     BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
     const int wpb = 4;   // waves per block
-    hipLaunchKernelGGL(build_A_entries, dim3((nent + wpb - 1) / wpb), dim3(64 * wpb), 0, 0, dF.as<double>(), nf,
-                       dT.as<double>(), k, eps, kernel_id, part, dist_series, use_ct, k_ct, toeplitz, nent, basis_id,
-                       toeplitz ? dV.as<double>() : dO.as<double>());
+    hipLaunchKernelGGL(build_A_entries, dim3((nent + wpb - 1) / wpb), dim3(64 * wpb), 0, 0, dF.p, nf,
+                       dT.p, k, eps, kernel_id, part, dist_series, use_ct, k_ct, toeplitz, nent, basis_id,
+                       toeplitz ? dV.p : dO.p);
     BDRT_HIP(hipGetLastError());
     if (toeplitz) {
         double c0, r0;
-        BDRT_HIP(hipMemcpy(&c0, dV.as<double>(), sizeof(double), hipMemcpyDeviceToHost));
-        BDRT_HIP(hipMemcpy(&r0, dV.as<double>() + nf, sizeof(double), hipMemcpyDeviceToHost));
+        BDRT_HIP(hipMemcpy(&c0, dV.p, sizeof(double), hipMemcpyDeviceToHost));
+        BDRT_HIP(hipMemcpy(&r0, dV.p + nf, sizeof(double), hipMemcpyDeviceToHost));
         if (!(c0 == r0)) {                       // matrices.py:239-241
             set_error("First entries of first row and column are not equal (%.17g vs %.17g)", r0, c0);
             return -2;
         }
-        hipLaunchKernelGGL(toeplitz_expand, dim3((nf * k + 255) / 256), dim3(256), 0, 0, dV.as<double>(), nf, k,
-                           dO.as<double>());
+        hipLaunchKernelGGL(toeplitz_expand, dim3((nf * k + 255) / 256), dim3(256), 0, 0, dV.p, nf, k,
+                           dO.p);
         BDRT_HIP(hipGetLastError());
     }
     BDRT_HIP(hipMemcpy(out, dO.p, (size_t)nf * k * sizeof(double), hipMemcpyDeviceToHost));
@@ -257,16 +249,15 @@ int bdrt_build_L_rect(const double *freq, int nf, const double *tau, int k, doub
         return -1;
     }
     bind_process_device();
-    DevBuf dF, dT, dO;
-    int rc;
-    if ((rc = dT.alloc(k * sizeof(double))) || (rc = dO.alloc((size_t)nf * k * sizeof(double)))) return rc;
+    DevBuf<double> dF, dT, dO;
+    BDRT_HIP(dT.alloc(k)); BDRT_HIP(dO.alloc((size_t)nf * k));
     if (freq) {
-        if ((rc = dF.alloc(nf * sizeof(double)))) return rc;
+        BDRT_HIP(dF.alloc(nf));
         BDRT_HIP(hipMemcpy(dF.p, freq, nf * sizeof(double), hipMemcpyHostToDevice));
     }
     BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(build_L_kernel, dim3((nf * k + 255) / 256), dim3(256), 0, 0, freq ? dF.as<double>() : (const double *)nullptr,
-                       nf, dT.as<double>(), k, eps, coef4[0], coef4[1], coef4[2], coef4[3], basis_id, dO.as<double>());
+    hipLaunchKernelGGL(build_L_kernel, dim3((nf * k + 255) / 256), dim3(256), 0, 0, freq ? dF.p : (const double *)nullptr,
+                       nf, dT.p, k, eps, coef4[0], coef4[1], coef4[2], coef4[3], basis_id, dO.p);
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipMemcpy(out, dO.p, (size_t)nf * k * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
@@ -276,12 +267,11 @@ int bdrt_build_M(const double *tau, int k, double eps, const double *coef3, int 
 {
     if (!tau || !coef3 || !out || k <= 0) { set_error("bdrt_build_M: bad arguments"); return -1; }
     bind_process_device();
-    DevBuf dT, dO;
-    int rc;
-    if ((rc = dT.alloc(k * sizeof(double))) || (rc = dO.alloc((size_t)k * k * sizeof(double)))) return rc;
+    DevBuf<double> dT, dO;
+    BDRT_HIP(dT.alloc(k)); BDRT_HIP(dO.alloc((size_t)k * k));
     BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(build_M_kernel, dim3((k * k + 255) / 256), dim3(256), 0, 0, dT.as<double>(), k, eps, coef3[0],
-                       coef3[1], coef3[2], toeplitz, dO.as<double>());
+    hipLaunchKernelGGL(build_M_kernel, dim3((k * k + 255) / 256), dim3(256), 0, 0, dT.p, k, eps, coef3[0],
+                       coef3[1], coef3[2], toeplitz, dO.p);
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipMemcpy(out, dO.p, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost));
     return 0;

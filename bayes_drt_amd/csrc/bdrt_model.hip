@@ -281,7 +281,7 @@ static int build_problem(Problem &P, const bdrt_dat *dat)
             !getenv("BDRT_STREAM_A")) {
             D.toepA = 1;
             D.tlen = (8 + nf + D.blk[0].K - 1 + 8 + 1) & ~1;
-            // (the sampler's theta rows, bdrt_nuts.hip::nuts_lds_bytes; with outlier parameters its state stays in HBM)
+            // (the sampler's theta rows, bdrt_sampler.hip::nuts_lds_bytes; with outlier parameters its state stays in HBM)
             const size_t nj = D.outlier_mode ? 0 : s1_nj(D.D);
             if ((s1_lds_doubles(D) + (size_t)NC * 32 * nj) * sizeof(double) + SAMPLER_LDS_RESERVE > 160 * 1024) { D.toepA = 0; D.tlen = 0; }
         }

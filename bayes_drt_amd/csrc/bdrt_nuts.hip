@@ -1,4 +1,6 @@
-// bdrt_nuts.hip -- device-resident NUTS (replaces StanModel.sampling, reference bayes_drt/inversion.py:1218-1221).
+// bdrt_nuts.hip -- device-resident NUTS (replaces StanModel.sampling, reference bayes_drt/inversion.py:1218-1221): the one-chain-per-
+// workgroup, streamed and re-layout kernels, the launchers of these and of the 16-chain kernel (bdrt_nuts_launch.h), and the few-point
+// evaluator / device L-BFGS that launch kernels of this file.  The sampler's host side is bdrt_sampler.hip.
 //
 // MI355X design: one workgroup owns 16 chains for the whole run.  Every loop iteration is one leapfrog for those
 // 16 chains: kick/drift (vector pass), the MFMA log-posterior+gradient tile (bdrt_device.h), second kick, then the
@@ -22,31 +24,12 @@
 #include <cstring>
 #include <type_traits>
 
-#include "bdrt_host.h"
-#include "bdrt_lbfgs.h"
-#include "bdrt_nuts_device.h"
-#include "bdrt_solo.h"
-#include "bdrt_wave.h"
-#include "bdrt_nuts_args.h"
-#include "bdrt_big.h"
+#include "bdrt_nuts_launch.h"
 
 namespace bdrt {
-
-// one-chain-per-wave sampler / evaluator (bdrt_wave.hip)
-size_t wave_lds_request(const WaveGeom &g, int n_wg, int n_cu, int *nhot, int max_per_cu);
-int launch_wave_nuts(const DevProblem *dp, const NutsParams &np, const NutsArgs &args, const WaveGeom &g, int nhot, int n_wg, size_t lds,
-                     hipStream_t stream, int outlier_model);
-int launch_wave_eval(const DevProblem *dp, const WaveGeom &g, const double *d_theta, const int *d_spec, int B, int jacobian, double *d_lp,
-                     double *d_grad, int n_wg, size_t lds, hipStream_t stream, int outlier_model);
-
-}  // namespace bdrt
-#include "bdrt_nuts16.h"
-namespace bdrt {
-// (defined in bdrt_nuts_k0.hip .. bdrt_nuts_k4.hip)
+// (defined in bdrt_nuts_k0.hip .. bdrt_nuts_k5.hip)
 BDRT_NUTS16_G0(BDRT_NUTS16_DECLARE) BDRT_NUTS16_G1(BDRT_NUTS16_DECLARE) BDRT_NUTS16_G2(BDRT_NUTS16_DECLARE)
 BDRT_NUTS16_G3(BDRT_NUTS16_DECLARE) BDRT_NUTS16_G4(BDRT_NUTS16_DECLARE) BDRT_NUTS16_G5(BDRT_NUTS16_DECLARE_PROF)
-
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // One chain per workgroup (bdrt_solo.h): the same transition logic as nuts_kernel, element j of every vector in thread j,
@@ -428,18 +411,9 @@ __global__ __launch_bounds__(SOLO_NT, TIGHT ? 6 : 2) void solo_eval_kernel(const
 // One chain per workgroup, general block model (bdrt_solo_wide.h): the evaluation by 512 threads, everything after it by the
 // cooperative stage of bdrt_nuts_wide.h.  Global state layout: vecs [n_units][V_COUNT][ds] (the rows of nuts_kernel, one column).
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int W1_SCRATCH = 1600;                   // doubles of LDS for the cooperative stage (reductions, momentum normals)
 // rows of the chain kept in LDS for the launch, most used first (as many as fit: `nhot`): a plain leaf then touches HBM only
 // for the trajectory ends / higher checkpoint levels it rarely needs
 __device__ __constant__ signed char W1_HOT_ORDER[12] = {V_TH, V_P, V_G, V_MINV, V_CKP, V_THQ, V_GQ, V_CKP + 1, V_CKC + 1, V_CKP + 2, V_CKC + 2, V_RHO};
-constexpr int W1_HOT_MAX = 12;
-
-__host__ __device__ inline size_t wide1_lds_bytes(const Wide1Geom &G, int ds, int nhot)
-{
-    return ((size_t)G.total + W1_SCRATCH + 2 + (size_t)nhot * ds) * sizeof(double) + sizeof(ChainState) + 64 + 64;
-}
-
-static_assert((W1_SCRATCH + 2) * sizeof(double) + sizeof(ChainState) + 128 <= 16384, "wide1_capable (bdrt_solo_wide.h) leaves 16 KiB beside the evaluator");
 
 template <bool PROF = false>
 __global__ __launch_bounds__(SOLO_NT) void nuts_wide1_kernel(const DevProblem *__restrict__ Pp, NutsParams np, NutsArgs a, Wide1Geom G, int nhot)
@@ -525,10 +499,6 @@ __global__ __launch_bounds__(SOLO_NT) void nuts_wide1_kernel(const DevProblem *_
 // distributions of 301 basis functions are 1821 parameters; 8 and 16: D <= 4096 / 8192, one distribution of 1200 basis functions
 // is 2409 -- these two keep most of the stage's rows in scratch memory: the streamed path is the slow path either way).  The
 // stage's LDS scratch holds the D momentum normals behind its 512 doubles of reduction scratch.
-constexpr int BIG_MAX_D = 8192;
-__host__ __device__ inline int big_njx(int D) { return D <= 1024 ? 2 : (D <= 2048 ? 4 : (D <= 4096 ? 8 : 16)); }
-__host__ __device__ inline int big_scratch_doubles(int njx) { return njx <= 2 ? W1_SCRATCH : 512 + 512 * njx + 64; }
-__host__ __device__ inline size_t nuts_big_lds_bytes(int njx = 2) { return (size_t)(big_scratch_doubles(njx) + 2 + 9 * 8) * sizeof(double) + sizeof(ChainState) + 128; }
 
 template <int NJX>
 __global__ __launch_bounds__(SOLO_NT) void nuts_big_kernel(const DevProblem *__restrict__ Pp, NutsParams np, NutsArgs a)
@@ -604,12 +574,9 @@ __global__ __launch_bounds__(SOLO_NT) void wide1_eval_kernel(const DevProblem *_
 }
 
 
-// The tail of a large run.  The 16-chain kernel advances every live chain by one leapfrog per ~33 us whatever the number of
-// live chains; a run lasts as long as its longest chain (BASELINE config 4: 0.33 .. 0.98 M leapfrogs per chain), and in the
-// tail most tile columns are empty.  Once the number of live chains is below what the one-chain-per-workgroup kernel
-// finishes faster (8.3 us per leapfrog, one chain per CU at a time: below ~4 chains per CU), the live chains move there:
-// this kernel copies a chain's rows from the 16-chain layout [wg][V_*][column][ds16] to [slot][SV_* / SG_*][dss].
-// Same counter-based random numbers and the same arithmetic up to summation order, so the chains continue as they were.
+// Hand-over of the tail of a large run (bdrt_sampler.hip: maybe_migrate_tail): copies a live chain's rows from the 16-chain layout
+// [wg][V_*][column][ds16] to the one-chain layout [slot][SV_* / SG_*][dss].  Same counter-based random numbers and the same
+// arithmetic up to summation order, so the chains continue as they were.
 __global__ void nuts_migrate_kernel(const double *v16, int ds16, const int *unit_loc, const int *unit_map, double *vsolo, int dss, int D)
 {
     const int slot = blockIdx.x, u = unit_map[slot];
@@ -645,12 +612,10 @@ __global__ void nuts_migrate_wide1_kernel(const double *v16, int ds, const int *
     if (threadIdx.x == 0) states[u].thsel = 0;
 }
 
-// Compaction of a large run.  A finished chain leaves its column of the 16-column MFMA tile empty, and a workgroup costs the
-// same ~33 us per round however few of its columns are live.  While there are more workgroups than CUs (more than 16 live
-// chains per CU), the live chains are therefore re-packed into fewer, full workgroups from time to time: workgroup `blockIdx.x`
-// of the NEW layout gathers the rows of its up to 16 units from wherever they sat in the old one.  Rows are copied verbatim and
-// every random number is keyed by (seed, chain id, iteration, ...), never by the slot, so the chains continue bit for bit
-// (tests/test_gpu_config4.py).  Empty slots get the finite placeholders of a fresh sampler (inverse metric 1, zeros elsewhere).
+// Compaction of a large run (bdrt_sampler.hip: maybe_compact): workgroup `blockIdx.x` of the NEW layout gathers the rows of its up
+// to 16 units from wherever they sat in the old one.  Rows are copied verbatim and every random number is keyed by (seed, chain id,
+// iteration, ...), never by the slot, so the chains continue bit for bit (tests/test_gpu_config4.py).  Empty slots get the finite
+// placeholders of a fresh sampler (inverse metric 1, zeros elsewhere).
 __global__ __launch_bounds__(256) void nuts_compact_kernel(const double *vold, const int *old_loc, const int *new_slot_unit,
                                                            double *vnew, int ds)
 {
@@ -673,103 +638,11 @@ __global__ __launch_bounds__(256) void nuts_compact_kernel(const double *vold, c
     }
 }
 
-// can two workgroups of the one-chain kernel share a CU for this problem (LDS of the trimmed variant)?
-static bool solo_duo_fits(const DevProblem &P)
-{
-    if (const char *e = getenv("BDRT_SOLO_DUO")) { if (atoi(e) == 0) return false; }
-    const SoloGeom g = solo_geometry(P.nf, P.blk[0].K, P.D);
-    return 2 * (((size_t)g.o_vec + (size_t)SOLO_NHOT * g.DSS) * sizeof(double) + 64) <= 160 * 1024;
-}
-
-// Which kernel advances the one-chain layout (state rows [unit][SG_COUNT][ds]) while `live` chains are running: the one-chain-per-
-// wave kernel from more than two live chains per CU on (measured at 81 x 161, profiles/r05/kernel_sweep.txt: up to two per CU two
-// 512-thread workgroups finish a round in 9.4 us; a third chain on any CU is a second turn for them, 14.6 us, against 13.1 us of
-// the wave kernel), up to the eight per CU it keeps resident.  BDRT_WAVE=1 / 0: always / never.
-static bool wave_pays(int live, int n_cu) { return live > 2 * n_cu; }
-static int wave_max_units(int n_cu, const DevProblem &P) { return wave_chains_per_cu(P) * n_cu; }      // (a ninth chain on any CU is a second turn of the machine: 31 us per round instead of 19)
-
 // liveness of every unit (1: the chain is still running), for the host's re-packing decision
 __global__ void nuts_live_kernel(const ChainState *states, int n, int *live)
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u < n) { const int ph = states[u].phase; live[u] = (ph == PH_INIT || ph == PH_EPS || ph == PH_TREE) ? 1 : 0; }
-}
-
-// device allocation freed on scope exit
-struct DevTmpBuf {
-    void *p = nullptr;
-    ~DevTmpBuf() { if (p) hipFree(p); }
-};
-
-struct Sampler {
-    Problem *prob = nullptr;
-    NutsParams np;
-    NutsArgs args;
-    int n_units = 0, n_wg = 0, D = 0;
-    size_t lds_bytes = 0;
-    bool use_s1 = false;     // S1 evaluator with theta rows resident in LDS (MODE 2)
-    bool s1_hbm = false;     // S1 evaluator, sampler state in HBM (MODE 3: outlier parameters, K near 192)
-    bool hw = false;         // general half-wave evaluator (MODE 4: several distributions, parallel blocks)
-    bool solo = false;       // one chain per workgroup, state in LDS (bdrt_solo.h): few chains of the headline family
-    SoloGeom geom;
-    bool wave = false;       // the one-chain layout may be advanced by the one-chain-per-WAVE kernel (bdrt_wave.h: same state layout)
-    int wave_force = -1;     // BDRT_WAVE: 1 always, 0 never (-1: by the number of live chains, wave_pays)
-    bool solo_ok = false;    // the 512-thread one-chain kernels take this problem (else the wave kernel advances the layout whatever `live`)
-    bool wave_last = false;  // the last launch used the wave kernel (bdrt_sampler_kind)
-    int live = 0;            // chains of the one-chain layout still running (after the last launch that read the done counter)
-    WaveGeom geomw;
-    bool wide1 = false;      // one chain per workgroup, general block model (bdrt_solo_wide.h): few chains of any other Toeplitz family
-    Wide1Geom geom1;
-    int nhot1 = 0;           // rows of the chain that kernel keeps in LDS
-    bool big = false;        // problem beyond the LDS budget (bdrt_big.h): the wide1 layout advanced by nuts_big_kernel
-    double *d_bigws = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms_total = 0.0;
-    int64_t n_launch = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    int *d_done = nullptr;
-    unsigned long long *d_leaps = nullptr;
-    int rounds_default = 256;
-    long long *d_prof = nullptr;
-    int prof_wg = 0;                  // workgroups d_prof was allocated for (the layout can change under it: compaction, tail migration)
-    // tail migration (nuts_migrate_kernel)
-    int *d_active = nullptr;          // live chains after the last launch of the 16-chain kernel
-    int n_cu = 256;
-    bool may_migrate = false, migrated = false;
-    double *vecs16 = nullptr;         // the 16-chain rows, kept until the sampler is destroyed
-    int *d_unit_map = nullptr;
-    int n_solo = 0;                   // workgroups of the one-chain-per-workgroup kernel (= n_units unless migrated)
-    // unit <-> slot of the 16-chain kernel (compaction: nuts_compact_kernel)
-    std::vector<int> slot_unit;       // host copy of args.slot_unit: [n_wg][16]
-    std::vector<int> unit_loc;        // unit -> wg * 16 + slot (-1: retired: the chain had finished when its workgroup was re-packed)
-    int *d_slot_unit = nullptr, *d_unit_loc = nullptr;
-    size_t vecs_capacity = 0;         // doubles allocated behind args.vecs
-    double *vecs_alt = nullptr;       // second buffer of the same size: re-packing ping-pongs between the two (no allocation,
-    int *d_slot_alt = nullptr;        //  hence no implicit device synchronisation, per pass)
-    int *d_live = nullptr;
-    bool may_compact = false;
-    int n_compactions = 0;
-};
-
-// as many LDS-resident rows as fit beside the evaluator (160 KiB minus a margin)
-static int wide1_hot_rows(const Wide1Geom &G, int ds)
-{
-    int n = W1_HOT_MAX;
-    while (n > 0 && wide1_lds_bytes(G, ds, n) > 158 * 1024) --n;
-    return n;
-}
-
-// what the 16-chain kernel keeps beside the tile region: lp / hand-over cells, chain states, spectrum ids / offsets / flags, and
-// the uniforms of sixteen leaves per chain
-constexpr size_t NUTS16_SCALAR_LDS = (size_t)3 * NC * sizeof(double) + NC * sizeof(ChainState) + 3 * NC * sizeof(int) + 16 + (size_t)NC * 16 * sizeof(double);
-static_assert(NUTS16_SCALAR_LDS <= SAMPLER_LDS_RESERVE,
-              "bdrt_problem_create reserves SAMPLER_LDS_RESERVE bytes for what the sampler keeps beside the tile region");
-static size_t nuts_lds_bytes(const DevProblem &P, bool s1)
-{
-    const int nj = s1_nj(P.D);
-    const size_t tile = s1 ? s1_lds_doubles(P) + (size_t)NC * 32 * nj : lds_doubles(P);   // s1: + theta rows
-    return tile * sizeof(double) + NUTS16_SCALAR_LDS;
 }
 
 // any_b: the caller wants ONE evaluator whatever the batch size (the Newton iteration's trial points: a fit's numbers must not depend on
@@ -847,13 +720,15 @@ int lbfgs_device(Problem &P, const double *x0, const int *spec, int n, const bdr
     } else {
         lds = ((size_t)G.total + 8) * sizeof(double) + 64;
     }
-    DevTmpBuf dx0, dxo, dgo, drep, dspec, dwork;
+    DevBuf<double> dx0, dxo, dgo, dwork;
+    DevBuf<LbfgsDevReport> drep;
+    DevBuf<int> dspec;
     const size_t nb = (size_t)n * D * sizeof(double);
-    BDRT_HIP(hipMalloc(&dx0.p, nb)); BDRT_HIP(hipMalloc(&dxo.p, nb)); BDRT_HIP(hipMalloc(&dgo.p, nb));
-    BDRT_HIP(hipMalloc(&drep.p, (size_t)n * sizeof(LbfgsDevReport)));
+    BDRT_HIP(dx0.alloc((size_t)n * D)); BDRT_HIP(dxo.alloc((size_t)n * D)); BDRT_HIP(dgo.alloc((size_t)n * D));
+    BDRT_HIP(drep.alloc((size_t)n));
     BDRT_HIP(hipMemcpy(dx0.p, x0, nb, hipMemcpyHostToDevice));
-    if (spec) { BDRT_HIP(hipMalloc(&dspec.p, (size_t)n * sizeof(int))); BDRT_HIP(hipMemcpy(dspec.p, spec, (size_t)n * sizeof(int), hipMemcpyHostToDevice)); }
-    if (!solo) BDRT_HIP(hipMalloc(&dwork.p, (size_t)n * LBFGS_WIDE_ROWS * DS * sizeof(double)));
+    if (spec) { BDRT_HIP(dspec.alloc((size_t)n)); BDRT_HIP(hipMemcpy(dspec.p, spec, (size_t)n * sizeof(int), hipMemcpyHostToDevice)); }
+    if (!solo) BDRT_HIP(dwork.alloc((size_t)n * LBFGS_WIDE_ROWS * DS));
     const long long cap = (long long)std::max(o.max_iter, 0) * 4 + 64;
     const int max_evals = (int)std::min<long long>(cap, 1LL << 30);
     static LdsAttrCache attr_s, attr_w;
@@ -876,13 +751,83 @@ int lbfgs_device(Problem &P, const double *x0, const int *spec, int n, const bdr
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Launchers (bdrt_nuts_launch.h).  ONE table holds every sampler instantiation under its key; its 16-chain part IS the list of
+// bdrt_nuts16.h (BDRT_NUTS16_G0..G5): an instantiation added to a group can be launched and has its LDS limit raised, a key in
+// no group is an error.  (The table stands AFTER the evaluator / L-BFGS launchers above and names the one-chain kernels in this
+// order on purpose: templates are instantiated in the order of first use, and lbfgs_kernel<true> compiles differently otherwise.)
+// ---------------------------------------------------------------------------------------------------------------------------
+struct NutsEntry {
+    NutsKey key;
+    bool prof;
+    int n_threads;
+    const void *fn;
+};
+#define BDRT_NUTS16_ENTRY(NJ_, MODE_, TA_) {{NutsFamily::tile16, NJ_, MODE_, TA_}, false, NT, (const void *)nuts_kernel<NJ_, MODE_, TA_, false>},
+#define BDRT_NUTS16_ENTRY_PROF(NJ_, MODE_, TA_) {{NutsFamily::tile16, NJ_, MODE_, TA_}, true, NT, (const void *)nuts_kernel<NJ_, MODE_, TA_, true>},
+#define BDRT_NUTS1_ENTRY(FAMILY_, A_, PROF_, ...) {{NutsFamily::FAMILY_, A_, 0, 0}, PROF_, SOLO_NT, (const void *)__VA_ARGS__},
+static const NutsEntry nuts_table[] = {
+    BDRT_NUTS1_ENTRY(solo, 2, false, nuts_solo_kernel<2, false>) BDRT_NUTS1_ENTRY(solo, 4, false, nuts_solo_kernel<4, false>)
+    BDRT_NUTS1_ENTRY(solo, 2, true, nuts_solo_kernel<2, true>) BDRT_NUTS1_ENTRY(solo, 4, true, nuts_solo_kernel<4, true>)
+    BDRT_NUTS1_ENTRY(wide1, 0, false, nuts_wide1_kernel<false>) BDRT_NUTS1_ENTRY(wide1, 0, true, nuts_wide1_kernel<true>)
+    BDRT_NUTS1_ENTRY(big, 2, false, nuts_big_kernel<2>) BDRT_NUTS1_ENTRY(big, 4, false, nuts_big_kernel<4>)
+    BDRT_NUTS1_ENTRY(big, 8, false, nuts_big_kernel<8>) BDRT_NUTS1_ENTRY(big, 16, false, nuts_big_kernel<16>)
+    BDRT_NUTS16_G0(BDRT_NUTS16_ENTRY) BDRT_NUTS16_G1(BDRT_NUTS16_ENTRY) BDRT_NUTS16_G2(BDRT_NUTS16_ENTRY)
+    BDRT_NUTS16_G3(BDRT_NUTS16_ENTRY) BDRT_NUTS16_G4(BDRT_NUTS16_ENTRY) BDRT_NUTS16_G5(BDRT_NUTS16_ENTRY_PROF)};
+#undef BDRT_NUTS16_ENTRY
+#undef BDRT_NUTS16_ENTRY_PROF
+#undef BDRT_NUTS1_ENTRY
+
+hipError_t nuts_set_lds_limit(size_t bytes)
+{
+    static LdsAttrCache cache;
+    return cache.ensure(bytes, [&]() {
+        hipError_t e = hipSuccess;
+        for (const auto &k : nuts_table)              // (the streamed kernels keep the default limit)
+            if (e == hipSuccess && k.key.family != NutsFamily::big) e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        return e;
+    });
+}
+
+int launch_nuts(NutsKey key, const DevProblem *dp, const NutsParams &np, const NutsArgs &args, int n_wg, size_t lds, hipStream_t stream,
+                const void *extra0, const void *extra1)
+{
+    const NutsEntry *plain = nullptr, *prof = nullptr;
+    for (const auto &k : nuts_table)
+        if (k.key.family == key.family && k.key.a == key.a && k.key.b == key.b && k.key.c == key.c) (k.prof ? prof : plain) = &k;
+    if (!plain) { set_error("no sampler kernel of family %d with key <%d, %d, %d>", (int)key.family, key.a, key.b, key.c); return -11; }
+    void *argv[] = {(void *)&dp, (void *)&np, (void *)&args, (void *)extra0, (void *)extra1};
+    const NutsEntry &k = args.prof && prof ? *prof : *plain;
+    BDRT_HIP(hipLaunchKernel(k.fn, dim3(n_wg), dim3(k.n_threads), argv, lds, stream));
+    return 0;
+}
+
+int launch_nuts_live(const ChainState *states, int n_units, int *live, hipStream_t stream)
+{
+    hipLaunchKernelGGL(nuts_live_kernel, dim3((n_units + 255) / 256), dim3(256), 0, stream, states, n_units, live);
+    BDRT_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_nuts_migrate(bool to_solo, const double *v16, int ds16, const int *unit_loc, const int *unit_map, int n_tail, double *vnew, int dss,
+                        int D, ChainState *states, hipStream_t stream)
+{
+    if (to_solo) hipLaunchKernelGGL(nuts_migrate_kernel, dim3((unsigned)n_tail), dim3(256), 0, stream, v16, ds16, unit_loc, unit_map, vnew, dss, D);
+    else hipLaunchKernelGGL(nuts_migrate_wide1_kernel, dim3((unsigned)n_tail), dim3(256), 0, stream, v16, ds16, unit_loc, unit_map, vnew, states);
+    BDRT_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_nuts_compact(const double *vold, const int *old_loc, const int *new_slot_unit, int n_wg, double *vnew, int ds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(nuts_compact_kernel, dim3(n_wg), dim3(256), 0, stream, vold, old_loc, new_slot_unit, vnew, ds);
+    BDRT_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace bdrt
 
 using namespace bdrt;
-
-struct bdrt_sampler {
-    bdrt::Sampler impl;
-};
 
 // test probe (tests/test_gpu_lean_math.py): a leaf's acceptance decision and new log-weight in the device form of nuts_leaf_joins (one
 // exponential) and in the textbook form (log_sum_exp2, u < exp(w - lsw_new)) -- both with the device's lean exp / log
@@ -901,793 +846,57 @@ __global__ void leaf_joins_probe_kernel(const double *lsw_sub, const double *w, 
 
 extern "C" {
 
-void bdrt_nuts_defaults(bdrt_nuts_control *c)
+/* parity-test hooks (not part of include/bdrt.h): one of the one-chain evaluators on B points -- the one-chain-per-workgroup path's
+   (bdrt_solo.h), the one-chain-per-wave path's (bdrt_wave.h), the general one (bdrt_solo_wide.h) */
+enum class DebugEval { solo, wave, wide1 };
+static int debug_logp_grad(DebugEval which, const char *who, bdrt_problem *p, const double *theta, const int *spec, int B, int jacobian,
+                           double *lp, double *grad)
 {
-    c->adapt_delta = 0.9; c->adapt_t0 = 10; c->adapt_gamma = 0.05; c->adapt_kappa = 0.75;
-    c->max_treedepth = 10; c->init_buffer = 75; c->term_buffer = 50; c->base_window = 25;
-    c->init_radius = 2; c->max_deltaH = 1000; c->stepsize0 = 1;
-}
-
-void bdrt_sampler_destroy(bdrt_sampler *s)
-{
-    if (!s) return;
-    Sampler &S = s->impl;
-    if (S.stream) hipStreamSynchronize(S.stream);
-    for (auto &pr : S.pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (S.args.vecs) hipFree(S.args.vecs);
-    if (S.args.states) hipFree(S.args.states);
-    if (S.args.draws) hipFree(S.args.draws);
-    if (S.args.lp_draws) hipFree(S.args.lp_draws);
-    if (S.d_done) hipFree(S.d_done);
-    if (S.d_leaps) hipFree(S.d_leaps);
-    if (S.d_prof) hipFree(S.d_prof);
-    if (S.d_active) hipFree(S.d_active);
-    if (S.d_bigws) hipFree(S.d_bigws);
-    if (S.vecs16) hipFree(S.vecs16);
-    if (S.d_unit_map) hipFree(S.d_unit_map);
-    if (S.d_slot_unit) hipFree(S.d_slot_unit);
-    if (S.d_unit_loc) hipFree(S.d_unit_loc);
-    if (S.vecs_alt) hipFree(S.vecs_alt);
-    if (S.d_slot_alt) hipFree(S.d_slot_alt);
-    if (S.d_live) hipFree(S.d_live);
-    if (S.stream) hipStreamDestroy(S.stream);
-    delete s;
-}
-
-bdrt_sampler *bdrt_sampler_create(bdrt_problem *p, int n_units, const int *spec, const int *chain_id, int warmup,
-                                  int n_draws, uint64_t seed, const double *init_theta, const bdrt_nuts_control *ctrl)
-{
-    if (!p || n_units < 1 || warmup < 0 || n_draws < 0) { set_error("bdrt_sampler_create: bad arguments"); return nullptr; }
-    bdrt_nuts_control c;
-    if (ctrl) c = *ctrl; else bdrt_nuts_defaults(&c);
-    if (c.max_treedepth < 1 || c.max_treedepth > MAXD) { set_error("max_treedepth must be in [1,%d]", MAXD); return nullptr; }
-    // Stan's argument checks (stan::services: adapt delta in (0,1), gamma / kappa / t0 / stepsize > 0, init radius >= 0); written so
-    // that NaN fails them.  Nonsense here does not crash a kernel, it silently gives nonsense chains.
-    if (!(c.adapt_delta > 0.0 && c.adapt_delta < 1.0)) { set_error("bdrt_sampler_create: adapt_delta must be in (0,1)"); return nullptr; }
-    if (!(c.adapt_gamma > 0.0) || !(c.adapt_kappa > 0.0) || !(c.adapt_t0 > 0.0)) { set_error("bdrt_sampler_create: adapt_gamma, adapt_kappa, adapt_t0 must be positive"); return nullptr; }
-    if (!(c.stepsize0 > 0.0) || !std::isfinite(c.stepsize0)) { set_error("bdrt_sampler_create: stepsize0 must be positive and finite"); return nullptr; }
-    if (!(c.init_radius >= 0.0) || !std::isfinite(c.init_radius)) { set_error("bdrt_sampler_create: init_radius must be >= 0 and finite"); return nullptr; }
-    if (!(c.max_deltaH > 0.0)) { set_error("bdrt_sampler_create: max_deltaH must be positive"); return nullptr; }
-    if (c.init_buffer < 0 || c.term_buffer < 0 || c.base_window < 0) { set_error("bdrt_sampler_create: adaptation window sizes must be >= 0"); return nullptr; }
+    if (!p || !theta || B < 1) { set_error("%s: bad arguments", who); return -1; }
     Problem &P = p->impl;
-    if (hipSetDevice(P.device) != hipSuccess) { set_error("bdrt_sampler_create: hipSetDevice(%d) failed", P.device); return nullptr; }
-    bdrt_sampler *s = new bdrt_sampler();
-    Sampler &S = s->impl;
-    memset(&S.args, 0, sizeof(S.args));
-    S.prob = &P;
-    S.n_units = n_units;
-    // few chains of the headline family on log-uniform grids: one chain per workgroup (bdrt_solo.h)
-    int n_cu = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, P.device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    }
-    // (measured at 81 x 161, profiles/r03/solo_duo.txt: one workgroup per CU 30.6 M evals/s, two per CU 42-45 M from 512 units on;
-    //  the 16-chain kernel passes that at ~1300 units)
-    S.solo = solo_capable(P.dev) && n_units <= (solo_duo_fits(P.dev) ? 5 * n_cu : 4 * n_cu);
-    S.n_cu = n_cu;
-    // a run that starts on the 16-chain kernel may hand its last live chains to the one-chain-per-workgroup kernel
-    S.may_migrate = (solo_capable(P.dev) || wide1_capable(P.dev) || wave_capable(P.dev)) && !S.solo;
-    if (const char *e = getenv("BDRT_SOLO")) {                                                  // diagnostics: force / forbid
-        S.solo = solo_capable(P.dev) && atoi(e) != 0;
-        S.may_migrate = false;
-    }
-    if (const char *e = getenv("BDRT_TAIL_MIGRATION")) S.may_migrate = S.may_migrate && atoi(e) != 0;
-    if (getenv("BDRT_WIDE1") && atoi(getenv("BDRT_WIDE1")) == 0 && !solo_capable(P.dev)) S.may_migrate = false;
-    // one chain per wave (bdrt_wave.h) for the one-chain layout: BDRT_WAVE=1 whenever the problem allows, 0 never
-    S.solo_ok = solo_capable(P.dev);
-    // (families without the LDS-resident one-chain kernel -- the outlier error models: up to one chain per CU the general one-chain kernel
-    //  is the faster one, 12.9 against 16.9 us per round at 256 units; from there to four per CU the wave kernel, 53 against 29 M evals/s
-    //  at 1024 units: profiles/r05/wave_outliers.txt)
-    S.wave = wave_capable(P.dev);
-    if (const char *e = getenv("BDRT_WAVE")) { S.wave_force = atoi(e) != 0; S.wave = S.wave && S.wave_force; }
-    if (getenv("BDRT_CHAINS_PER_WG")) S.wave = false;                                           // (a forced packing means the 16-chain kernel)
-    if (getenv("BDRT_SOLO") && S.wave_force != 1) S.wave = false;                                // (BDRT_SOLO=0 / 1: the 16-chain kernel / the 512-thread one-chain kernels, forced)
-    if (S.wave && !getenv("BDRT_SOLO") && (S.wave_force == 1 || (n_units <= wave_max_units(n_cu, P.dev) && (wave_pays(n_units, n_cu) || (!S.solo_ok && (n_units > n_cu || !wide1_capable(P.dev))))))) {
-        S.solo = true;                                                                          // start in the one-chain layout
-        S.may_migrate = false;
-    }
-    if (S.wave) S.geomw = wave_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
-    if (S.solo) S.geom = solo_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D);
-    // chains per workgroup: fill every CU with one workgroup before putting a second chain on any wave
-    {
-        int cpw = (n_units + n_cu - 1) / n_cu;
-        if (const char *e = getenv("BDRT_CHAINS_PER_WG")) cpw = atoi(e);     // diagnostics: force a packing
-        S.args.cpw = S.solo ? 1 : std::min(NC, std::max(1, cpw));
-    }
-    S.n_wg = (n_units + S.args.cpw - 1) / S.args.cpw;
-    S.D = P.dev.D;
-    // few chains of a model the LDS-resident kernel does not cover: still one chain per workgroup, evaluated by 512 threads
-    S.wide1 = !S.solo && n_units <= (11 * n_cu) / 4 && wide1_capable(P.dev);    // (measured at D = 818: 12.7 M evals/s from 256 units on; the 16-chain kernel passes that at ~750)
-    if (const char *e = getenv("BDRT_WIDE1")) S.wide1 = S.wide1 && atoi(e) != 0;                // diagnostics: forbid
-    if (getenv("BDRT_CHAINS_PER_WG")) S.wide1 = false;                                          // (a forced packing means the 16-chain kernel)
-    if (S.wide1) {
-        S.geom1 = wide1_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
-        S.args.cpw = 1; S.n_wg = n_units;
-        S.may_migrate = false;
-    }
-    // a problem beyond the LDS budget of the tile evaluators (bdrt_big.h): one chain per workgroup in the same row layout, the
-    // streamed evaluator, whatever the number of units
-    S.big = P.dev.big != 0 && !S.wide1;
-    if (S.big) {
-        S.solo = false; S.wave = false; S.wide1 = true;
-        S.args.cpw = 1; S.n_wg = n_units;
-        S.may_migrate = false;
-    }
-    S.np.warmup = warmup; S.np.n_draws = n_draws; S.np.max_depth = c.max_treedepth;
-    S.np.delta = c.adapt_delta; S.np.gamma = c.adapt_gamma; S.np.t0 = c.adapt_t0; S.np.kappa = c.adapt_kappa;
-    S.np.init_radius = c.init_radius; S.np.max_deltaH = c.max_deltaH; S.np.stepsize0 = c.stepsize0;
-    S.np.seed_lo = (uint32_t)seed; S.np.seed_hi = (uint32_t)(seed >> 32);
-    S.np.has_init = init_theta != nullptr;
-    // the fast S1 kernel (theta rows resident in LDS) when the problem takes that path and the rows fit
-    S.use_s1 = P.dev.fast_s1 && P.dev.outlier_mode == 0 && P.dev.D <= 2 * RW && P.dev.D <= 32 * 16 &&
-               nuts_lds_bytes(P.dev, true) <= 160 * 1024;
-    S.s1_hbm = !S.use_s1 && P.dev.fast_s1 && P.dev.D <= 32 * 16;
-    S.hw = P.dev.fast_hw && P.dev.D <= 32 * 27;
-    if (S.s1_hbm || S.hw)
-        S.lds_bytes = (S.hw ? hw_lds_doubles(P.dev) : s1_lds_doubles(P.dev)) * sizeof(double) + NUTS16_SCALAR_LDS;
-    else
-        S.lds_bytes = nuts_lds_bytes(P.dev, S.use_s1);
-    if (S.wide1 && !S.big) {
-        const int ds1 = S.D <= 32 * 11 ? 32 * 11 : (S.D <= 32 * 16 ? 32 * 16 : 32 * 27);
-        S.nhot1 = wide1_hot_rows(S.geom1, ds1);
-        S.lds_bytes = std::max(S.lds_bytes, wide1_lds_bytes(S.geom1, ds1, S.nhot1));     // (one attribute value for every kernel)
-    }
-    if (S.big) S.lds_bytes = nuts_big_lds_bytes(big_njx(S.D));
-    auto fail = [&](const char *msg) -> bdrt_sampler * { set_error("%s", msg); bdrt_sampler_destroy(s); return nullptr; };
-    if (S.lds_bytes > 160 * 1024) return fail("bdrt_sampler_create: problem too large for the 160 KiB LDS budget");
-    for (int u = 0; u < n_units; ++u)
-        if (spec && (spec[u] < 0 || spec[u] >= P.dev.n_spectra)) return fail("bdrt_sampler_create: spectrum index out of range");
-
-    // row stride of the state vectors = 32*NJ of the kernel instantiation; the solo kernel keeps [unit][row][ds] with one column
-    const int DS = S.solo ? S.geom.DSS : (S.use_s1 ? 32 * s1_nj(S.D) : (S.D <= 32 * 11 ? 32 * 11 : (S.D <= 32 * 16 ? 32 * 16 : (S.D <= 32 * 27 ? 32 * 27 : 512 * big_njx(S.D)))));
-    if (S.D > (S.big ? BIG_MAX_D : 32 * 27)) {
-        set_error("bdrt_sampler_create: D = %d > %d not supported", S.D, S.big ? BIG_MAX_D : 864); bdrt_sampler_destroy(s); return nullptr;
-    }
-    S.args.ds = DS;
-    const int ncol = (S.solo || S.wide1) ? 1 : NC, nrow = S.solo ? (int)SG_COUNT : (int)V_COUNT;
-    const int r_minv = S.solo ? (int)SV_MINV : (int)V_MINV, r_th = S.solo ? (int)SV_TH : (int)V_TH;
-    if (S.solo && S.solo_ok) S.lds_bytes = (size_t)S.geom.total * sizeof(double) + 64;
-    const size_t nvec = (size_t)S.n_wg * nrow * ncol * DS;
-    std::vector<double> hv(nvec, 0.0);
-    std::vector<ChainState> hs((size_t)n_units);
-    for (int u = 0; u < n_units; ++u) {
-        ChainState &st = hs[u];
-        memset(&st, 0, sizeof(st));
-        st.phase = PH_INIT;
-        st.z_iter = -1;
-        st.spec = spec ? spec[u] : 0;
-        st.chain_id = chain_id ? chain_id[u] : u;
-        st.eps = c.stepsize0;
-        st.dir = 1;
-        st.lsw_sub = -INFINITY;
-        window_init(st, warmup, c.init_buffer, c.term_buffer, c.base_window);
-        const int wg = u / S.args.cpw, cc = (S.solo || S.wide1) ? 0 : slot_col(u % S.args.cpw);
-        double *V = hv.data() + (size_t)wg * nrow * ncol * DS;
-        const Philox rng = {S.np.seed_lo, S.np.seed_hi, (uint32_t)st.chain_id};
-        for (int j = 0; j < S.D; ++j) {
-            V[((size_t)r_minv * ncol + cc) * DS + j] = 1.0;
-            V[((size_t)r_th * ncol + cc) * DS + j] =
-                init_theta ? init_theta[(size_t)u * S.D + j]
-                           : c.init_radius * (2.0 * rng_uniform(rng, (uint32_t)j, RNG_INIT, 0, 0, 0) - 1.0);
-        }
-        if (!init_theta) st.init_attempt = 0;
-    }
-    // unused columns (cpw < 16, last workgroup): finite placeholders
-    for (int wg = 0; wg < S.n_wg && !S.solo && !S.wide1; ++wg)
-        for (int k = 0; k < NC; ++k) {
-            if (k < S.args.cpw && wg * S.args.cpw + k < n_units) continue;
-            double *V = hv.data() + (size_t)wg * V_COUNT * NC * DS;
-            for (int j = 0; j < S.D; ++j) V[((size_t)V_MINV * NC + slot_col(k)) * DS + j] = 1.0;
-        }
-    if (!S.solo && !S.wide1) {
-        S.slot_unit.assign((size_t)S.n_wg * NC, -1);
-        S.unit_loc.assign((size_t)n_units, -1);
-        for (int u = 0; u < n_units; ++u) {
-            const int wg = u / S.args.cpw, k = u % S.args.cpw;
-            S.slot_unit[(size_t)wg * NC + k] = u;
-            S.unit_loc[u] = wg * NC + k;
-        }
-        if (hipMalloc((void **)&S.d_slot_unit, S.slot_unit.size() * sizeof(int)) != hipSuccess) return fail("hipMalloc(slot map) failed");
-        if (hipMalloc((void **)&S.d_unit_loc, S.unit_loc.size() * sizeof(int)) != hipSuccess) return fail("hipMalloc(slot map) failed");
-        if (hipMemcpy(S.d_slot_unit, S.slot_unit.data(), S.slot_unit.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(S.d_unit_loc, S.unit_loc.data(), S.unit_loc.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-            return fail("bdrt_sampler_create: upload of the slot map failed");
-        S.args.slot_unit = S.d_slot_unit;
-        // more workgroups than CUs: finished chains can be squeezed out of the tiles (BDRT_COMPACTION=0 keeps the layout)
-        S.may_compact = S.n_wg > n_cu && !(getenv("BDRT_COMPACTION") && atoi(getenv("BDRT_COMPACTION")) == 0);
-    }
-    S.vecs_capacity = nvec;
-    if (hipMalloc((void **)&S.args.vecs, nvec * sizeof(double)) != hipSuccess) return fail("hipMalloc(vecs) failed");
-    if (hipMalloc((void **)&S.args.states, hs.size() * sizeof(ChainState)) != hipSuccess) return fail("hipMalloc(states) failed");
-    const size_t nd = (size_t)n_units * std::max(n_draws, 1) * S.D;
-    if (hipMalloc((void **)&S.args.draws, nd * sizeof(double)) != hipSuccess) return fail("hipMalloc(draws) failed");
-    if (hipMalloc((void **)&S.args.lp_draws, (size_t)n_units * std::max(n_draws, 1) * sizeof(double)) != hipSuccess)
-        return fail("hipMalloc(lp) failed");
-    if (hipMalloc((void **)&S.d_done, sizeof(int)) != hipSuccess) return fail("hipMalloc failed");
-    if (hipMalloc((void **)&S.d_leaps, sizeof(unsigned long long)) != hipSuccess) return fail("hipMalloc failed");
-    if (hipMalloc((void **)&S.d_active, sizeof(int)) != hipSuccess) return fail("hipMalloc failed");
-    if (S.big && hipMalloc((void **)&S.d_bigws, (size_t)S.n_wg * big_ws_doubles(P.dev) * sizeof(double)) != hipSuccess) return fail("hipMalloc(workspace) failed");
-    S.args.bigws = S.d_bigws;
-    if (hipMemcpy(S.args.vecs, hv.data(), nvec * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail("bdrt_sampler_create: upload of the chain vectors failed");
-    if (hipMemcpy(S.args.states, hs.data(), hs.size() * sizeof(ChainState), hipMemcpyHostToDevice) != hipSuccess)
-        return fail("bdrt_sampler_create: upload of the chain states failed");
-    if (hipMemset(S.args.draws, 0, nd * sizeof(double)) != hipSuccess) return fail("bdrt_sampler_create: clearing the draws failed");
-    if (hipMemset(S.d_leaps, 0, sizeof(unsigned long long)) != hipSuccess)
-        return fail("bdrt_sampler_create: clearing the leapfrog counter failed");
-    // hipMemset returns before the fill has happened, and the sampler's kernels run on a NON-BLOCKING stream that does not order
-    // itself behind the null stream: without this wait a launch that follows quickly (several host threads sampling at once)
-    // can have its first draws / its leapfrog counter zeroed under it.
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail("bdrt_sampler_create: initial fills failed");
-    S.args.leap_counter = S.d_leaps;
-    S.args.done_counter = S.d_done;
-    S.args.active_counter = S.d_active;
-    S.args.unit_map = nullptr;
-    S.n_solo = n_units;
-    S.live = n_units;
-    S.args.n_units = n_units;
-    if (hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
-    static LdsAttrCache attr_cache;
-    const hipError_t ae = attr_cache.ensure(S.lds_bytes, [&]() {
-        const void *fns[38] = {(const void *)nuts_kernel<11, 2, 1, true>, (const void *)nuts_kernel<11, 2, 2, true>,
-                               (const void *)nuts_kernel<7, 2, 2, true>, (const void *)nuts_kernel<27, 4, 0, true>,
-                               (const void *)nuts_kernel<4, 2, 2>, (const void *)nuts_kernel<6, 2, 2>, (const void *)nuts_kernel<7, 2, 2>,
-                               (const void *)nuts_kernel<4, 2, 0>, (const void *)nuts_kernel<6, 2, 0>, (const void *)nuts_kernel<7, 2, 0>,
-                               (const void *)nuts_kernel<6, 2, 1>,
-                               (const void *)nuts_kernel<11, 2, 2>, (const void *)nuts_kernel<16, 2, 2>,
-                               (const void *)nuts_kernel<11, 2, 1>, (const void *)nuts_kernel<16, 2, 1>,
-                               (const void *)nuts_kernel<11, 1>, (const void *)nuts_kernel<11, 0>,
-                               (const void *)nuts_kernel<16, 1>, (const void *)nuts_kernel<16, 0>,
-                               (const void *)nuts_kernel<27, 1>, (const void *)nuts_kernel<27, 0>,
-                               (const void *)nuts_kernel<11, 2>, (const void *)nuts_kernel<16, 2>,
-                               (const void *)nuts_kernel<11, 3>, (const void *)nuts_kernel<16, 3>,
-                               (const void *)nuts_kernel<11, 4>, (const void *)nuts_kernel<16, 4>, (const void *)nuts_kernel<27, 4>,
-                               (const void *)nuts_kernel<11, 3, 3>, (const void *)nuts_kernel<16, 3, 3>, (const void *)nuts_kernel<11, 3, 4>,
-                               (const void *)nuts_kernel<16, 3, 4>, (const void *)nuts_kernel<11, 4, 3>, (const void *)nuts_kernel<16, 4, 3>,
-                               (const void *)nuts_kernel<27, 4, 3>, (const void *)nuts_kernel<11, 4, 4>, (const void *)nuts_kernel<16, 4, 4>,
-                               (const void *)nuts_kernel<27, 4, 4>};
-        hipError_t e = hipFuncSetAttribute((const void *)nuts_solo_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)nuts_solo_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)nuts_solo_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)nuts_solo_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)nuts_wide1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)nuts_wide1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        for (int i = 0; i < 38 && e == hipSuccess; ++i)
-            e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes);
-        return e;
-    });
-    if (ae != hipSuccess) {
-        set_error("hipFuncSetAttribute(nuts_kernel, %zu B dynamic LDS) failed: %s", S.lds_bytes, hipGetErrorString(ae));
-        bdrt_sampler_destroy(s);
-        return nullptr;
-    }
-    return s;
-}
-
-static int harvest_events(Sampler &S, bool wait)
-{
-    size_t k = 0;
-    for (; k < S.pending.size(); ++k) {
-        auto &pr = S.pending[k];
-        if (!wait && hipEventQuery(pr.second) != hipSuccess) break;
-        if (wait) BDRT_HIP(hipEventSynchronize(pr.second));
-        float ms = 0.f;
-        BDRT_HIP(hipEventElapsedTime(&ms, pr.first, pr.second));
-        S.ms_total += ms;
-        hipEventDestroy(pr.first); hipEventDestroy(pr.second);
-    }
-    S.pending.erase(S.pending.begin(), S.pending.begin() + k);
-    return 0;
-}
-
-int bdrt_sampler_advance(bdrt_sampler *s, int rounds, int *all_done)
-{
-    if (!s || rounds < 1) { set_error("bdrt_sampler_advance: bad arguments"); return -1; }
-    Sampler &S = s->impl;
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    S.args.rounds = rounds;
-    BDRT_HIP(hipMemsetAsync(S.d_done, 0, sizeof(int), S.stream));
-    BDRT_HIP(hipMemsetAsync(S.d_active, 0, sizeof(int), S.stream));
-    hipEvent_t e0, e1;
-    BDRT_HIP(hipEventCreate(&e0));
-    BDRT_HIP(hipEventCreate(&e1));
-    BDRT_HIP(hipEventRecord(e0, S.stream));
-    {
-        const DevProblem *dp = (const DevProblem *)S.prob->d_dev;
-        const bool tp = S.prob->dev.toep_all != 0;
-#define BDRT_LAUNCH_NUTS(NJV)                                                                                          \
-        do {                                                                                                           \
-            if (tp) hipLaunchKernelGGL((nuts_kernel<NJV, 1>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args); \
-            else hipLaunchKernelGGL((nuts_kernel<NJV, 0>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args);   \
-        } while (0)
-        if (S.big && S.D <= 1024)
-            hipLaunchKernelGGL(nuts_big_kernel<2>, dim3(S.n_wg), dim3(SOLO_NT), nuts_big_lds_bytes(2), S.stream, dp, S.np, S.args);
-        else if (S.big && S.D <= 2048)
-            hipLaunchKernelGGL(nuts_big_kernel<4>, dim3(S.n_wg), dim3(SOLO_NT), nuts_big_lds_bytes(4), S.stream, dp, S.np, S.args);
-        else if (S.big && S.D <= 4096)
-            hipLaunchKernelGGL(nuts_big_kernel<8>, dim3(S.n_wg), dim3(SOLO_NT), nuts_big_lds_bytes(8), S.stream, dp, S.np, S.args);
-        else if (S.big)
-            hipLaunchKernelGGL(nuts_big_kernel<16>, dim3(S.n_wg), dim3(SOLO_NT), nuts_big_lds_bytes(16), S.stream, dp, S.np, S.args);
-        else if (S.wide1 && S.args.prof)
-            hipLaunchKernelGGL(nuts_wide1_kernel<true>, dim3(S.n_wg), dim3(SOLO_NT), wide1_lds_bytes(S.geom1, S.args.ds, S.nhot1), S.stream, dp,
-                               S.np, S.args, S.geom1, S.nhot1);
-        else if (S.wide1)
-            hipLaunchKernelGGL(nuts_wide1_kernel<false>, dim3(S.n_wg), dim3(SOLO_NT), wide1_lds_bytes(S.geom1, S.args.ds, S.nhot1), S.stream, dp,
-                               S.np, S.args, S.geom1, S.nhot1);
-        else if (S.solo && S.wave && (S.wave_force == 1 || !S.solo_ok || wave_pays(S.live, S.n_cu)))
-        {
-            // LDS share (= chains per CU) by the chains still running: finished ones leave their wave at once
-            int nhot = 0;
-            const size_t lds = wave_lds_request(S.geomw, std::max(1, std::min(S.live, S.n_solo)), S.n_cu, &nhot, wave_chains_per_cu(S.prob->dev));
-            if (launch_wave_nuts(dp, S.np, S.args, S.geomw, nhot, S.n_solo, lds, S.stream, S.prob->dev.outlier_mode != 0)) return -10;
-            S.wave_last = true;
-        }
-        else if (S.solo)
-        {
-            S.wave_last = false;
-            // more chains than CUs: two workgroups per CU (128 VGPRs each, 16 of the chain's rows in LDS) overlap each other's
-            // latencies; with at most one chain per CU the full-LDS variant is the faster one.  BDRT_SOLO_DUO=0 / 1: never / always.
-            const size_t lds2 = ((size_t)S.geom.o_vec + (size_t)SOLO_NHOT * S.geom.DSS) * sizeof(double) + 64;
-            const char *e = getenv("BDRT_SOLO_DUO");
-            const bool duo = 2 * lds2 <= 160 * 1024 && (e ? atoi(e) != 0 : S.n_solo > S.n_cu);
-            if (duo && S.args.prof)
-                hipLaunchKernelGGL((nuts_solo_kernel<4, true>), dim3(S.n_solo), dim3(SOLO_NT), lds2, S.stream, dp, S.np, S.args, S.geom);
-            else if (duo)
-                hipLaunchKernelGGL(nuts_solo_kernel<4>, dim3(S.n_solo), dim3(SOLO_NT), lds2, S.stream, dp, S.np, S.args, S.geom);
-            else if (S.args.prof)
-                hipLaunchKernelGGL((nuts_solo_kernel<2, true>), dim3(S.n_solo), dim3(SOLO_NT), S.lds_bytes, S.stream, dp, S.np, S.args, S.geom);
-            else
-                hipLaunchKernelGGL(nuts_solo_kernel<2>, dim3(S.n_solo), dim3(SOLO_NT), S.lds_bytes, S.stream, dp, S.np, S.args, S.geom);
-        }
-        else if (S.use_s1) {
-            const int nj = S.args.ds / 32, ta = S.prob->dev.toepA;
-#define BDRT_S1_NUTS(NJ_, TA_) hipLaunchKernelGGL((nuts_kernel<NJ_, 2, TA_>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args)
-#define BDRT_S1_NUTS_PROF(NJ_, TA_) hipLaunchKernelGGL((nuts_kernel<NJ_, 2, TA_, true>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args)
-            // (the phase profile is filled by the profiling instantiations: the headline family's and BASELINE config 5's)
-            if (S.args.prof && nj == 11 && ta == 1) BDRT_S1_NUTS_PROF(11, 1);
-            else if (S.args.prof && nj == 11 && ta == 2) BDRT_S1_NUTS_PROF(11, 2);
-            else if (S.args.prof && nj == 7 && ta == 2) BDRT_S1_NUTS_PROF(7, 2);
-            else
-            if (nj == 4) { if (ta == 2) BDRT_S1_NUTS(4, 2); else BDRT_S1_NUTS(4, 0); }
-            else if (nj == 6) { if (ta == 2) BDRT_S1_NUTS(6, 2); else if (ta == 1) BDRT_S1_NUTS(6, 1); else BDRT_S1_NUTS(6, 0); }
-            else if (nj == 7) { if (ta == 2) BDRT_S1_NUTS(7, 2); else BDRT_S1_NUTS(7, 0); }
-            else if (nj == 11) { if (ta == 2) BDRT_S1_NUTS(11, 2); else if (ta == 1) BDRT_S1_NUTS(11, 1); else BDRT_S1_NUTS(11, 0); }
-            else { if (ta == 2) BDRT_S1_NUTS(16, 2); else if (ta == 1) BDRT_S1_NUTS(16, 1); else BDRT_S1_NUTS(16, 0); }
-#undef BDRT_S1_NUTS
-#undef BDRT_S1_NUTS_PROF
-        }
-        else if (S.s1_hbm || S.hw) {
-            // the evaluator's instantiation by the longest basis (3, 4 or 6 basis functions per lane)
-            const int kmax = S.hw ? hw_kmax(S.prob->dev) : S.prob->dev.blk[0].K;
-            static const bool ku6 = getenv("BDRT_S1_KU") && atoi(getenv("BDRT_S1_KU")) == 6;     // (measurements: the K <= 192 instantiation)
-            const int ku = ku6 ? 0 : (kmax <= 96 ? 3 : (kmax <= 128 ? 4 : 0));
-            const int nj = S.D <= 32 * 11 ? 11 : (S.D <= 32 * 16 ? 16 : 27);
-#define BDRT_X_NUTS(NJ_, MODE_, KU_) hipLaunchKernelGGL((nuts_kernel<NJ_, MODE_, KU_>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args)
-#define BDRT_X_KU(NJ_, MODE_) do { if (ku == 3) BDRT_X_NUTS(NJ_, MODE_, 3); else if (ku == 4) BDRT_X_NUTS(NJ_, MODE_, 4); else BDRT_X_NUTS(NJ_, MODE_, 0); } while (0)
-            if (S.s1_hbm) { if (nj == 11) BDRT_X_KU(11, 3); else BDRT_X_KU(16, 3); }
-            else if (nj == 11) BDRT_X_KU(11, 4);
-            else if (nj == 16) BDRT_X_KU(16, 4);
-            else if (S.args.prof && ku == 0) hipLaunchKernelGGL((nuts_kernel<27, 4, 0, true>), dim3(S.n_wg), dim3(NT), S.lds_bytes, S.stream, dp, S.np, S.args);
-            else BDRT_X_KU(27, 4);
-#undef BDRT_X_KU
-#undef BDRT_X_NUTS
-        }
-        else if (S.D <= 32 * 11) BDRT_LAUNCH_NUTS(11);
-        else if (S.D <= 32 * 16) BDRT_LAUNCH_NUTS(16);
-        else BDRT_LAUNCH_NUTS(27);
-#undef BDRT_LAUNCH_NUTS
+    const DevProblem *dp = (const DevProblem *)P.d_dev;
+    if (which == DebugEval::solo && !solo_capable(P.dev)) { set_error("problem does not take the solo path"); return -2; }
+    if (which == DebugEval::wave && !wave_capable(P.dev)) { set_error("problem does not take the one-chain-per-wave path"); return -2; }
+    if (which == DebugEval::wide1 && !wide1_capable(P.dev)) { set_error("problem does not take the general one-chain evaluator"); return -2; }
+    BDRT_HIP(hipSetDevice(P.device));
+    DevBuf<double> dth, dlp, dg;
+    DevBuf<int> dsp;
+    const size_t n = (size_t)B * P.dev.D;
+    BDRT_HIP(dth.alloc(n)); BDRT_HIP(dg.alloc(n)); BDRT_HIP(dlp.alloc(B));
+    BDRT_HIP(hipMemcpy(dth, theta, n * sizeof(double), hipMemcpyHostToDevice));
+    BDRT_HIP(hipMemset(dg, 0, n * sizeof(double)));
+    if (spec) { BDRT_HIP(dsp.alloc(B)); BDRT_HIP(hipMemcpy(dsp, spec, B * sizeof(int), hipMemcpyHostToDevice)); }
+    if (which == DebugEval::solo) {
+        const SoloGeom g = solo_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D);
+        const size_t lds = solo_eval_lds_bytes(g);
+        BDRT_HIP(hipFuncSetAttribute((const void *)solo_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(solo_eval_kernel<false>, dim3(B), dim3(SOLO_NT), lds, 0, dp, g, dth.p, dsp.p, B, jacobian, dlp.p, dg.p);
+    } else if (which == DebugEval::wave) {
+        const WaveGeom g = wave_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
+        if (const int rc = launch_wave_eval(dp, g, dth, dsp, B, jacobian, dlp, dg, std::min(B, 2048), wave_lds_bytes(g, 0), 0, P.dev.outlier_mode != 0)) return rc;
+    } else {
+        const Wide1Geom G = wide1_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
+        const size_t lds = (size_t)G.total * sizeof(double) + 64;
+        BDRT_HIP(hipFuncSetAttribute((const void *)wide1_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(wide1_eval_kernel, dim3(B), dim3(SOLO_NT), lds, 0, dp, G, dth.p, dsp.p, B, jacobian, dlp.p, dg.p);
     }
     BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipEventRecord(e1, S.stream));
-    S.pending.emplace_back(e0, e1);
-    S.n_launch += 1;
-    if (all_done) {
-        int done = 0;
-        BDRT_HIP(hipMemcpyAsync(&done, S.d_done, sizeof(int), hipMemcpyDeviceToHost, S.stream));
-        BDRT_HIP(hipStreamSynchronize(S.stream));
-        *all_done = done >= S.n_wg;
-        if (S.solo) S.live = std::max(0, S.n_solo - done);
-        return harvest_events(S, true);
-    }
-    return harvest_events(S, false);
-}
-
-int bdrt_sampler_sync(bdrt_sampler *s)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    // the live-chain count that picks the next launch's kernel (one chain per wave / per workgroup, the wave kernel's LDS share):
-    // `advance(..., NULL)` does not read the launch's done counter back, a sync does (the last launch wrote it)
-    if (S.solo && S.n_launch > 0) {
-        int done = 0;
-        BDRT_HIP(hipMemcpy(&done, S.d_done, sizeof(int), hipMemcpyDeviceToHost));
-        S.live = std::max(0, S.n_solo - done);
-    }
-    return harvest_events(S, true);
-}
-
-// frees its device pointers unless they were handed over (error paths of the two re-layout passes below)
-struct DevTmp {
-    void *p = nullptr;
-    ~DevTmp() { if (p) hipFree(p); }
-    void *release() { void *q = p; p = nullptr; return q; }
-};
-
-// Re-pack the live chains of a 16-chain run into fewer workgroups (nuts_compact_kernel).  Called between launches with the
-// stream idle and `active` = live chains after the last launch.  Worth it only while the run has more workgroups than CUs:
-// with one workgroup per CU a round costs the same whatever the number of live columns, and fewer workgroups would only idle CUs.
-static int maybe_compact(Sampler &S, int active)
-{
-    if (!S.may_compact || S.migrated || S.solo || S.wide1 || active <= 0) return 0;
-    const int target = std::max(S.n_cu, (active + NC - 1) / NC);
-    // A launch runs its workgroups in turns of one per CU, and every turn lasts the full `rounds` however many CUs it fills:
-    // what a re-packing buys is a whole turn, so it is done when -- and only when -- the live chains fit in one turn less
-    // (measured on 1536 spectra x 8 chains: re-packing at every 1/16 of the workgroups, 15 passes, 32.7 s; at the turn
-    // boundaries 8192 and 4096 live chains ... see profiles/r03/oversubscribed.txt; frozen layout 36.6 s)
-    if ((target + S.n_cu - 1) / S.n_cu >= (S.n_wg + S.n_cu - 1) / S.n_cu) return 0;
-    if (!S.vecs_alt) {
-        // the second buffer and the liveness flags, once (keep going as is when the memory is not there)
-        if (hipMalloc((void **)&S.vecs_alt, S.vecs_capacity * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); S.vecs_alt = nullptr; S.may_compact = false; return 0; }
-        if (hipMalloc((void **)&S.d_slot_alt, S.slot_unit.size() * sizeof(int)) != hipSuccess ||
-            hipMalloc((void **)&S.d_live, (size_t)S.n_units * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); S.may_compact = false; return 0; }
-    }
-    std::vector<int> alive((size_t)S.n_units);
-    hipLaunchKernelGGL(nuts_live_kernel, dim3((S.n_units + 255) / 256), dim3(256), 0, S.stream, (const ChainState *)S.args.states, S.n_units, S.d_live);
-    BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipMemcpyAsync(alive.data(), S.d_live, alive.size() * sizeof(int), hipMemcpyDeviceToHost, S.stream));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    std::vector<int> live;
-    for (int wgk = 0; wgk < (int)S.slot_unit.size(); ++wgk) {            // slot order: keeps neighbours (same spectrum) together
-        const int u = S.slot_unit[wgk];
-        if (u >= 0 && alive[u]) live.push_back(u);
-    }
-    if (live.empty()) return 0;
-    const int n_wg = std::max(std::min(S.n_cu, (int)live.size()), ((int)live.size() + NC - 1) / NC);
-    const int cpw = ((int)live.size() + n_wg - 1) / n_wg;
-    std::vector<int> slot_unit((size_t)n_wg * NC, -1), unit_loc((size_t)S.n_units, -1);
-    for (size_t i = 0; i < live.size(); ++i) {
-        const int wg = (int)(i / cpw), k = (int)(i % cpw);
-        slot_unit[(size_t)wg * NC + k] = live[i];
-        unit_loc[live[i]] = wg * NC + k;
-    }
-    BDRT_HIP(hipMemcpyAsync(S.d_slot_alt, slot_unit.data(), slot_unit.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    // d_unit_loc still holds the OLD locations: the kernel reads them, then they are replaced
-    hipLaunchKernelGGL(nuts_compact_kernel, dim3(n_wg), dim3(256), 0, S.stream, (const double *)S.args.vecs, (const int *)S.d_unit_loc,
-                       (const int *)S.d_slot_alt, S.vecs_alt, S.args.ds);
-    BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipMemcpyAsync(S.d_unit_loc, unit_loc.data(), unit_loc.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    BDRT_HIP(hipStreamSynchronize(S.stream));            // (the host vectors above are read by the asynchronous copies)
-    std::swap(S.args.vecs, S.vecs_alt);
-    std::swap(S.d_slot_unit, S.d_slot_alt);
-    S.args.slot_unit = S.d_slot_unit;
-    S.slot_unit.swap(slot_unit);
-    S.unit_loc.swap(unit_loc);
-    S.n_wg = n_wg;
-    S.n_compactions += 1;
-    if (S.d_prof) { S.args.prof = nullptr; }              // (the phase-profile slots were laid out for the old workgroups)
+    BDRT_HIP(hipDeviceSynchronize());
+    if (lp) BDRT_HIP(hipMemcpy(lp, dlp, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad) BDRT_HIP(hipMemcpy(grad, dg, n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
-
-// Hand the live chains of a 16-chain run to the one-chain-per-workgroup kernel when that finishes them sooner (see
-// nuts_migrate_kernel).  Called between launches with the stream idle.
-static int maybe_migrate_tail(Sampler &S, int active)
-{
-    // the one-chain kernels run one or two chains per CU at a time, ~4x faster per leapfrog: the LDS-resident one wins below ~4.75
-    // live chains per CU when two of its workgroups fit a CU (else ~3.5), the general one below ~2.75
-    const bool to_solo = solo_capable(S.prob->dev) || S.wave;
-    // (the one-chain-per-wave kernel runs eight chains per CU at 108 M evals/s against 73 M of half-empty tiles: profiles/r04/wave_sweep.txt)
-    const int limit = S.wave ? wave_chains_per_cu(S.prob->dev) * S.n_cu : (to_solo ? (solo_duo_fits(S.prob->dev) ? (19 * S.n_cu) / 4 : (7 * S.n_cu) / 2) : (11 * S.n_cu) / 4);
-    if (active <= 0 || active > limit) return 0;
-    std::vector<ChainState> hs((size_t)S.n_units);
-    BDRT_HIP(hipMemcpy(hs.data(), S.args.states, hs.size() * sizeof(ChainState), hipMemcpyDeviceToHost));
-    std::vector<int> map;
-    for (int u = 0; u < S.n_units; ++u)
-        if (hs[u].phase == PH_INIT || hs[u].phase == PH_EPS || hs[u].phase == PH_TREE) map.push_back(u);
-    if (map.empty()) return 0;
-    DevTmp vnew, dmap;
-    if (!to_solo) {
-        // general one-chain kernel: the 16-chain rows, one column
-        const Wide1Geom G = wide1_geometry(S.prob->dev.nf, S.prob->dev.blk[0].K, S.prob->dev.D, S.prob->dev.nblocks);
-        int nhot = W1_HOT_MAX;                                // as many LDS-resident rows as the LDS limit set at creation allows
-        while (nhot > 0 && wide1_lds_bytes(G, S.args.ds, nhot) > std::min(S.lds_bytes, (size_t)158 * 1024)) --nhot;
-        if (wide1_lds_bytes(G, S.args.ds, nhot) > S.lds_bytes) return 0;
-        if (hipMalloc(&vnew.p, map.size() * (size_t)V_COUNT * S.args.ds * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        if (hipMalloc(&dmap.p, map.size() * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        BDRT_HIP(hipMemcpy(dmap.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nuts_migrate_wide1_kernel, dim3((unsigned)map.size()), dim3(256), 0, S.stream, (const double *)S.args.vecs, S.args.ds,
-                           (const int *)S.d_unit_loc, (const int *)dmap.p, (double *)vnew.p, S.args.states);
-        BDRT_HIP(hipGetLastError());
-        BDRT_HIP(hipStreamSynchronize(S.stream));
-        S.vecs16 = S.args.vecs;
-        S.args.prof = nullptr;
-        S.args.vecs = (double *)vnew.release();
-        S.d_unit_map = (int *)dmap.release();
-        S.args.unit_map = S.d_unit_map;
-        S.geom1 = G;
-        S.nhot1 = nhot;
-        S.wide1 = true;
-        S.n_solo = (int)map.size();
-        S.n_wg = S.n_solo;
-        S.migrated = true;
-        return 0;
-    }
-    const SoloGeom g = solo_geometry(S.prob->dev.nf, S.prob->dev.blk[0].K, S.prob->dev.D);
-    const size_t lds = (size_t)g.total * sizeof(double) + 64;
-    if (S.solo_ok && lds > S.lds_bytes) return 0;         // (bdrt_sampler_create raised every kernel's LDS limit to the 16-chain size)
-    if (hipMalloc(&vnew.p, map.size() * (size_t)SG_COUNT * g.DSS * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 0; }   // (keep going as is)
-    if (hipMalloc(&dmap.p, map.size() * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    BDRT_HIP(hipMemcpy(dmap.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(nuts_migrate_kernel, dim3((unsigned)map.size()), dim3(256), 0, S.stream, (const double *)S.args.vecs, S.args.ds,
-                       (const int *)S.d_unit_loc, (const int *)dmap.p, (double *)vnew.p, g.DSS, S.D);
-    BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    S.vecs16 = S.args.vecs;
-    S.args.prof = nullptr;                                // (the phase-profile slots are laid out per 16-chain workgroup)
-    S.args.vecs = (double *)vnew.release();
-    S.args.ds = g.DSS;
-    S.d_unit_map = (int *)dmap.release();
-    S.args.unit_map = S.d_unit_map;
-    S.geom = g;
-    S.lds_bytes = lds;
-    S.solo = true;
-    S.n_solo = (int)map.size();
-    S.live = S.n_solo;
-    S.n_wg = S.n_solo;                                   // (the all-done test counts finished workgroups)
-    S.migrated = true;
-    return 0;
-}
-
-int bdrt_sampler_run(bdrt_sampler *s)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    // upper bound on the leapfrogs one chain can need: (2^depth - 1 + step-size trials) per iteration
-    const long long per_iter = (1LL << S.np.max_depth) + 64;
-    const long long bound = per_iter * (S.np.warmup + S.np.n_draws + 2) + 200;
-    long long spent = 0;
-    int done = 0;
-    while (!done && spent <= bound) {
-        int rc = bdrt_sampler_advance(s, S.rounds_default, &done);
-        if (rc) return rc;
-        spent += S.rounds_default;
-        if (!done && !S.migrated && (S.may_migrate || S.may_compact)) {
-            int active = 0;
-            BDRT_HIP(hipMemcpy(&active, S.d_active, sizeof(int), hipMemcpyDeviceToHost));
-            if (S.may_migrate && (rc = maybe_migrate_tail(S, active))) return rc;
-            if (!S.migrated && (rc = maybe_compact(S, active))) return rc;
-        }
-    }
-    if (!done) { set_error("bdrt_sampler_run: chains did not finish within the leapfrog bound"); return -3; }
-    return 0;
-}
-
-int bdrt_sampler_results(bdrt_sampler *s, double *draws, double *lp, bdrt_chain_diag *diag)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const size_t nd = (size_t)S.n_units * S.np.n_draws;
-    if (draws && nd) BDRT_HIP(hipMemcpy(draws, S.args.draws, nd * S.D * sizeof(double), hipMemcpyDeviceToHost));
-    if (lp && nd) BDRT_HIP(hipMemcpy(lp, S.args.lp_draws, nd * sizeof(double), hipMemcpyDeviceToHost));
-    if (diag) {
-        std::vector<ChainState> hs((size_t)S.n_units);
-        BDRT_HIP(hipMemcpy(hs.data(), S.args.states, hs.size() * sizeof(ChainState), hipMemcpyDeviceToHost));
-        for (int u = 0; u < S.n_units; ++u) {
-            diag[u].n_leapfrog = hs[u].n_leap_total;
-            diag[u].n_divergent = hs[u].n_div;
-            diag[u].n_max_treedepth = hs[u].n_maxdepth;
-            diag[u].stepsize = hs[u].eps;
-            diag[u].mean_accept = hs[u].n_post ? hs[u].sum_accept / hs[u].n_post : 0.0;
-            if (hs[u].phase == PH_FAILED) diag[u].n_leapfrog = -1;
-        }
-    }
-    return 0;
-}
-
-int bdrt_sampler_tail_units(bdrt_sampler *s) { return s && s->impl.migrated ? s->impl.n_solo : 0; }
-int bdrt_sampler_compactions(bdrt_sampler *s) { return s ? s->impl.n_compactions : -1; }
-int bdrt_sampler_kind(bdrt_sampler *s)
-{
-    if (!s) return -1;
-    const Sampler &S = s->impl;
-    if (S.big) return 4;
-    if (S.wide1) return 2;
-    if (!S.solo) return 0;
-    // before the first launch: what the first launch will use
-    const bool w = S.n_launch ? S.wave_last : (S.wave && (S.wave_force == 1 || !S.solo_ok || wave_pays(S.live, S.n_cu)));
-    return w ? 3 : 1;
-}
-
-int64_t bdrt_sampler_total_leapfrogs(bdrt_sampler *s)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    unsigned long long v = 0;
-    if (hipStreamSynchronize(S.stream) != hipSuccess) return -1;
-    if (hipMemcpy(&v, S.d_leaps, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (int64_t)v;
-}
-
-int bdrt_sampler_kernel_time(bdrt_sampler *s, double *ms_total, int64_t *n_launches, int reset)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    int rc = harvest_events(S, true);
-    if (rc) return rc;
-    if (ms_total) *ms_total = S.ms_total;
-    if (n_launches) *n_launches = S.n_launch;
-    if (reset) { S.ms_total = 0.0; S.n_launch = 0; }
-    return 0;
-}
-
-int bdrt_sampler_phase_profile(bdrt_sampler *s, int enable, long long *cycles32)
-{
-    if (!s) return -1;
-    Sampler &S = s->impl;
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    // d_prof holds prof_wg workgroups' slots: the layout may have changed since (compaction, tail migration switch the profile off
-    // and can leave MORE workgroups than it was allocated for) -- every copy / fill below is sized by the allocation
-    if (cycles32) {
-        for (int k = 0; k < 32; ++k) cycles32[k] = 0;
-        if (S.d_prof) {
-            std::vector<long long> h((size_t)S.prof_wg * 32);
-            BDRT_HIP(hipMemcpy(h.data(), S.d_prof, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            for (int w = 0; w < S.prof_wg; ++w)
-                for (int k = 0; k < 32; ++k) cycles32[k] += h[(size_t)w * 32 + k];
-        }
-    }
-    if (S.d_prof && (!enable || S.prof_wg < S.n_wg)) { hipFree(S.d_prof); S.d_prof = nullptr; S.prof_wg = 0; }
-    if (enable && !S.d_prof) {
-        BDRT_HIP(hipMalloc((void **)&S.d_prof, (size_t)S.n_wg * 32 * sizeof(long long)));
-        S.prof_wg = S.n_wg;
-    }
-    if (S.d_prof) {
-        BDRT_HIP(hipMemset(S.d_prof, 0, (size_t)S.prof_wg * 32 * sizeof(long long)));
-        BDRT_HIP(hipStreamSynchronize(nullptr));        // (same ordering rule as in bdrt_sampler_create)
-    }
-    S.args.prof = S.d_prof;
-    return 0;
-}
-
-int bdrt_sampler_percentiles(bdrt_sampler *s, int unit_lo, int unit_hi, int col0, int ncols, const double *Phi, int M,
-                             const double *bias, const double *q, int nq, double *out)
-{
-    if (!s || !q || nq < 1 || !out) { set_error("bdrt_sampler_percentiles: null argument"); return -1; }
-    Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || col0 < 0 || ncols < 1 || col0 + ncols > S.D ||
-        (Phi && M < 1) || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_percentiles: bad unit / column range");
-        return -1;
-    }
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const long rows = (long)(unit_hi - unit_lo) * S.np.n_draws;
-    if (rows > (1L << 30)) { set_error("bdrt_sampler_percentiles: too many rows"); return -1; }
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D + col0;
-    return post_percentiles_device(dX, (int)rows, ncols, (long)S.D, Phi, M, bias, q, nq, out);
-}
-
-int bdrt_sampler_summary(bdrt_sampler *s, int unit_lo, int unit_hi, const double *q, int nq, double *mean, double *pct)
-{
-    if (!s || !q || nq < 1 || !pct) { set_error("bdrt_sampler_summary: null argument"); return -1; }
-    Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_summary: bad unit range");
-        return -1;
-    }
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const long rows = (long)(unit_hi - unit_lo) * S.np.n_draws;
-    if (rows > (1L << 30)) { set_error("bdrt_sampler_summary: too many rows"); return -1; }
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
-    return post_percentiles_device(dX, (int)rows, S.D, (long)S.D, nullptr, 0, nullptr, q, nq, pct, S.prob->is_pos.data(), mean);
-}
-
-int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, double *mean, double *sd,
-                             double *n_eff, double *rhat)
-{
-    if (!s || chains_per_group < 1) { set_error("bdrt_sampler_diagnostics: bad arguments"); return -1; }
-    Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || (unit_hi - unit_lo) % chains_per_group || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_diagnostics: bad unit range");
-        return -1;
-    }
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
-    return diagnostics_to_host(dX, (long)S.np.n_draws * S.D, (long)S.D, S.prob->is_pos.data(), (unit_hi - unit_lo) / chains_per_group,
-                               chains_per_group, S.np.n_draws, S.D, mean, sd, n_eff, rhat, S.stream);
-}
-
-const double *bdrt_sampler_draws_dev(bdrt_sampler *s)
-{
-    if (!s) return nullptr;
-    hipStreamSynchronize(s->impl.stream);
-    return s->impl.args.draws;
-}
-
-/* parity-test hook (not part of include/bdrt.h): the evaluator of the one-chain-per-workgroup path on B points */
 int bdrt_debug_solo_logp_grad(bdrt_problem *p, const double *theta, const int *spec, int B, int jacobian, double *lp, double *grad)
 {
-    if (!p || !theta || B < 1) { set_error("bdrt_debug_solo_logp_grad: bad arguments"); return -1; }
-    Problem &P = p->impl;
-    if (!solo_capable(P.dev)) { set_error("problem does not take the solo path"); return -2; }
-    BDRT_HIP(hipSetDevice(P.device));
-    const SoloGeom g = solo_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D);
-    const size_t lds = solo_eval_lds_bytes(g);
-    BDRT_HIP(hipFuncSetAttribute((const void *)solo_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    double *dth = nullptr, *dlp = nullptr, *dg = nullptr;
-    int *dsp = nullptr;
-    const size_t nb = (size_t)B * P.dev.D * sizeof(double);
-    BDRT_HIP(hipMalloc((void **)&dth, nb)); BDRT_HIP(hipMalloc((void **)&dg, nb)); BDRT_HIP(hipMalloc((void **)&dlp, B * sizeof(double)));
-    BDRT_HIP(hipMemcpy(dth, theta, nb, hipMemcpyHostToDevice));
-    if (spec) { BDRT_HIP(hipMalloc((void **)&dsp, B * sizeof(int))); BDRT_HIP(hipMemcpy(dsp, spec, B * sizeof(int), hipMemcpyHostToDevice)); }
-    hipLaunchKernelGGL(solo_eval_kernel<false>, dim3(B), dim3(SOLO_NT), lds, 0, (const DevProblem *)P.d_dev, g, dth, dsp, B, jacobian, dlp, dg);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && lp) e = hipMemcpy(lp, dlp, B * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && grad) e = hipMemcpy(grad, dg, nb, hipMemcpyDeviceToHost);
-    hipFree(dth); hipFree(dg); hipFree(dlp); hipFree(dsp);
-    if (e != hipSuccess) { set_error("bdrt_debug_solo_logp_grad: %s", hipGetErrorString(e)); return -10; }
-    return 0;
+    return debug_logp_grad(DebugEval::solo, "bdrt_debug_solo_logp_grad", p, theta, spec, B, jacobian, lp, grad);
 }
-
-// the one-chain-per-wave evaluator (bdrt_wave.h) on B points: parity tests
 int bdrt_debug_wave_logp_grad(bdrt_problem *p, const double *theta, const int *spec, int B, int jacobian, double *lp, double *grad)
 {
-    if (!p || !theta || B < 1) { set_error("bdrt_debug_wave_logp_grad: bad arguments"); return -1; }
-    Problem &P = p->impl;
-    if (!wave_capable(P.dev)) { set_error("problem does not take the one-chain-per-wave path"); return -2; }
-    BDRT_HIP(hipSetDevice(P.device));
-    const WaveGeom g = wave_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
-    const size_t lds = wave_lds_bytes(g, 0);
-    double *dth = nullptr, *dlp = nullptr, *dg = nullptr;
-    int *dsp = nullptr;
-    const size_t nb = (size_t)B * P.dev.D * sizeof(double);
-    BDRT_HIP(hipMalloc((void **)&dth, nb)); BDRT_HIP(hipMalloc((void **)&dg, nb)); BDRT_HIP(hipMalloc((void **)&dlp, B * sizeof(double)));
-    BDRT_HIP(hipMemcpy(dth, theta, nb, hipMemcpyHostToDevice));
-    if (spec) { BDRT_HIP(hipMalloc((void **)&dsp, B * sizeof(int))); BDRT_HIP(hipMemcpy(dsp, spec, B * sizeof(int), hipMemcpyHostToDevice)); }
-    int rc = launch_wave_eval((const DevProblem *)P.d_dev, g, dth, dsp, B, jacobian, dlp, dg, std::min(B, 2048), lds, 0, P.dev.outlier_mode != 0);
-    hipError_t e = rc ? hipErrorUnknown : hipDeviceSynchronize();
-    if (e == hipSuccess && lp) e = hipMemcpy(lp, dlp, B * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && grad) e = hipMemcpy(grad, dg, nb, hipMemcpyDeviceToHost);
-    hipFree(dth); hipFree(dg); hipFree(dlp); hipFree(dsp);
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("bdrt_debug_wave_logp_grad: %s", hipGetErrorString(e)); return -10; }
-    return 0;
+    return debug_logp_grad(DebugEval::wave, "bdrt_debug_wave_logp_grad", p, theta, spec, B, jacobian, lp, grad);
 }
-
 int bdrt_debug_wide1_logp_grad(bdrt_problem *p, const double *theta, const int *spec, int B, int jacobian, double *lp, double *grad)
 {
-    if (!p || !theta || B < 1) { set_error("bdrt_debug_wide1_logp_grad: bad arguments"); return -1; }
-    Problem &P = p->impl;
-    if (!wide1_capable(P.dev)) { set_error("problem does not take the general one-chain evaluator"); return -2; }
-    BDRT_HIP(hipSetDevice(P.device));
-    const Wide1Geom G = wide1_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D, P.dev.nblocks);
-    const size_t lds = (size_t)G.total * sizeof(double) + 64;
-    BDRT_HIP(hipFuncSetAttribute((const void *)wide1_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    double *dth = nullptr, *dlp = nullptr, *dg = nullptr;
-    int *dsp = nullptr;
-    const size_t nbytes = (size_t)B * P.dev.D * sizeof(double);
-    BDRT_HIP(hipMalloc((void **)&dth, nbytes)); BDRT_HIP(hipMalloc((void **)&dg, nbytes)); BDRT_HIP(hipMalloc((void **)&dlp, B * sizeof(double)));
-    BDRT_HIP(hipMemcpy(dth, theta, nbytes, hipMemcpyHostToDevice));
-    BDRT_HIP(hipMemset(dg, 0, nbytes));
-    if (spec) { BDRT_HIP(hipMalloc((void **)&dsp, B * sizeof(int))); BDRT_HIP(hipMemcpy(dsp, spec, B * sizeof(int), hipMemcpyHostToDevice)); }
-    hipLaunchKernelGGL(wide1_eval_kernel, dim3(B), dim3(SOLO_NT), lds, 0, (const DevProblem *)P.d_dev, G, dth, dsp, B, jacobian, dlp, dg);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && lp) e = hipMemcpy(lp, dlp, B * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && grad) e = hipMemcpy(grad, dg, nbytes, hipMemcpyDeviceToHost);
-    hipFree(dth); hipFree(dg); hipFree(dlp); hipFree(dsp);
-    if (e != hipSuccess) { set_error("bdrt_debug_wide1_logp_grad: %s", hipGetErrorString(e)); return -10; }
-    return 0;
+    return debug_logp_grad(DebugEval::wide1, "bdrt_debug_wide1_logp_grad", p, theta, spec, B, jacobian, lp, grad);
 }
 
 int bdrt_debug_leaf_joins(const double *lsw_sub, const double *w, const double *u, int n, double *lsw_dev, int *join_dev, double *lsw_ref,
@@ -1696,39 +905,20 @@ int bdrt_debug_leaf_joins(const double *lsw_sub, const double *w, const double *
     if (!lsw_sub || !w || !u || !lsw_dev || !join_dev || !lsw_ref || !join_ref || !prob_ref || n < 1) {
         set_error("bdrt_debug_leaf_joins: bad arguments"); return -1;
     }
-    // every device buffer is owned by this list: an error path frees what was allocated before it (the pattern of newton_polish_device)
-    std::vector<void *> owned;
-    auto cleanup = [&]() { for (void *q : owned) hipFree(q); };
-#define LJ_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    double *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int *di[2] = {nullptr, nullptr};
-    for (auto &q : d) { LJ_HIP(hipMalloc((void **)&q, (size_t)n * sizeof(double))); owned.push_back(q); }
-    for (auto &q : di) { LJ_HIP(hipMalloc((void **)&q, (size_t)n * sizeof(int))); owned.push_back(q); }
-    LJ_HIP(hipMemcpy(d[0], lsw_sub, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    LJ_HIP(hipMemcpy(d[1], w, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    LJ_HIP(hipMemcpy(d[2], u, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(leaf_joins_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d[0], d[1], d[2], n, d[3], di[0], d[4], di[1], d[5]);
-    LJ_HIP(hipGetLastError());
-    LJ_HIP(hipMemcpy(lsw_dev, d[3], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    LJ_HIP(hipMemcpy(join_dev, di[0], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    LJ_HIP(hipMemcpy(lsw_ref, d[4], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    LJ_HIP(hipMemcpy(join_ref, di[1], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    LJ_HIP(hipMemcpy(prob_ref, d[5], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-#undef LJ_HIP
-    cleanup();
+    DevBuf<double> d[6];
+    DevBuf<int> di[2];
+    for (auto &q : d) BDRT_HIP(q.alloc((size_t)n));
+    for (auto &q : di) BDRT_HIP(q.alloc((size_t)n));
+    const double *in[3] = {lsw_sub, w, u};
+    for (int k = 0; k < 3; ++k) BDRT_HIP(hipMemcpy(d[k], in[k], (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(leaf_joins_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d[0].p, d[1].p, d[2].p, n, d[3].p, di[0].p, d[4].p, di[1].p, d[5].p);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipMemcpy(lsw_dev, d[3], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    BDRT_HIP(hipMemcpy(join_dev, di[0], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    BDRT_HIP(hipMemcpy(lsw_ref, d[4], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    BDRT_HIP(hipMemcpy(join_ref, di[1], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    BDRT_HIP(hipMemcpy(prob_ref, d[5], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
-}
-
-int bdrt_sample(bdrt_problem *p, int n_units, const int *spec, const int *chain_id, int warmup, int n_draws,
-                uint64_t seed, const double *init_theta, const bdrt_nuts_control *ctrl, double *draws, double *lp,
-                bdrt_chain_diag *diag)
-{
-    bdrt_sampler *s = bdrt_sampler_create(p, n_units, spec, chain_id, warmup, n_draws, seed, init_theta, ctrl);
-    if (!s) return -1;
-    int rc = bdrt_sampler_run(s);
-    if (rc == 0) rc = bdrt_sampler_results(s, draws, lp, diag);
-    bdrt_sampler_destroy(s);
-    return rc;
 }
 
 }  // extern "C"

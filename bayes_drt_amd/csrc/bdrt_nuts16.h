@@ -1,6 +1,6 @@
 // bdrt_nuts16.h -- the 16-chains-per-workgroup NUTS kernel (device-resident NUTS, replaces StanModel.sampling, reference
 // bayes_drt/inversion.py:1218-1221).  A header so that its instantiations compile in several translation units
-// (bdrt_nuts_k*.hip) next to the host side in bdrt_nuts.hip, and so that tools can instantiate one kernel alone.
+// (bdrt_nuts_k*.hip) next to their launcher in bdrt_nuts.hip, and so that tools can instantiate one kernel alone.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -1039,8 +1039,8 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
     }
 }
 
-// ---- the instantiations, in groups of similar compile time: bdrt_nuts_k<g>.hip defines group g, bdrt_nuts.hip (the host side)
-//      declares them all `extern template`
+// ---- the instantiations, in groups of similar compile time: bdrt_nuts_k<g>.hip defines group g; bdrt_nuts.hip declares them all
+//      `extern template` and expands the same groups into its launch table (launch_nuts, nuts_set_lds_limit): THE list, once
 #define BDRT_NUTS16_G0(X) X(11, 2, 1) X(11, 2, 2) X(11, 2, 0) X(4, 2, 2) X(4, 2, 0) X(6, 2, 1)
 #define BDRT_NUTS16_G1(X) X(16, 2, 2) X(16, 2, 1) X(16, 2, 0) X(6, 2, 2) X(6, 2, 0) X(7, 2, 2) X(7, 2, 0)
 #define BDRT_NUTS16_G2(X) X(11, 1, 0) X(11, 0, 0) X(16, 1, 0) X(16, 0, 0) X(27, 1, 0) X(27, 0, 0)

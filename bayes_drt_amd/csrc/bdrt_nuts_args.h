@@ -1,5 +1,5 @@
 // bdrt_nuts_args.h -- launch arguments and register-resident chain state shared by the sampler kernels' translation units
-// (bdrt_nuts.hip: 16-chain and one-chain-per-workgroup kernels, host side; bdrt_wave.hip: one-chain-per-wave kernel).
+// (bdrt_nuts.hip: 16-chain and one-chain-per-workgroup kernels; bdrt_wave.hip: one-chain-per-wave kernel; bdrt_sampler.hip: host side).
 #pragma once
 #include "bdrt_nuts_device.h"
 

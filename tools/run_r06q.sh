@@ -1,5 +1,5 @@
 #!/bin/bash
-# hyper-lambda iterations of the ridge starting point (BDRT_RIDGE_START_ITER, default 3): fit time and what the fits find
+# hyper-lambda iterations of the ridge starting point (BDRT_RIDGE_START_ITER, default 2): fit time and what the fits find
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/r06q
 for it in 3 2 1; do
   export BDRT_RIDGE_START_ITER=$it
