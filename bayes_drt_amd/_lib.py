@@ -75,9 +75,10 @@ SYMBOLS = [
     'bdrt_gram', 'bdrt_gram_batch', 'bdrt_qp_box', 'bdrt_qp_box_batch', 'bdrt_ridge', 'bdrt_ridge_ex',
     'bdrt_percentiles', 'bdrt_sampler_percentiles', 'bdrt_sampler_summary', 'bdrt_summary', 'bdrt_sampler_draws_dev',
     'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
+    'bdrt_rank_diagnostics', 'bdrt_sampler_rank_diagnostics', 'bdrt_rank_max_draws',
     'bdrt_pointwise_loglik', 'bdrt_psis_loo', 'bdrt_psis_loo_max_draws',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
-    'bdrt_debug_hessian', 'bdrt_debug_hessian_lin',
+    'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
 ]
 
 
@@ -183,6 +184,12 @@ def load_library():
     lib.bdrt_summary.argtypes = [vp, C.c_int, C.c_int, C.c_long, vp, vp, C.c_int, vp, vp]
     lib.bdrt_sampler_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.bdrt_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, vp, vp]
+    lib.bdrt_rank_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, C.c_double, C.c_double, vp, vp, vp,
+                                          vp, vp]
+    lib.bdrt_sampler_rank_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    lib.bdrt_rank_max_draws.argtypes = []
+    lib.bdrt_rank_max_draws.restype = C.c_int
+    lib.bdrt_debug_rank_z.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.bdrt_pointwise_loglik.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.bdrt_psis_loo.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.bdrt_psis_loo_max_draws.argtypes = []

@@ -128,6 +128,11 @@ int post_percentiles_device(const double *dX, int rows, int K, long ldx, const d
 int diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M, int N,
                         int C, double *mean, double *sd, double *n_eff, double *rhat, hipStream_t stream);
 
+// rank-normalised diagnostics (bdrt_rank.hip) of the same layout of DEVICE draws, on the split chains; outputs [G x C] on the host
+int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M,
+                             int N, int C, double p_lo, double p_hi, double *rhat, double *ess_bulk, double *ess_tail,
+                             double *ess_mean, double *sd, hipStream_t stream);
+
 // Levenberg-Marquardt Newton polish of n_fits points on the device (bdrt_newton.hip); x0 / x_out [n_fits][D] on the host
 int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
                          double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out);

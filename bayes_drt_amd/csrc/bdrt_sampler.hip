@@ -725,6 +725,23 @@ int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
                                chains_per_group, S.np.n_draws, S.D, mean, sd, n_eff, rhat, S.stream);
 }
 
+int bdrt_sampler_rank_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, double p_lo, double p_hi,
+                                  double *rhat, double *ess_bulk, double *ess_tail, double *ess_mean, double *sd)
+{
+    if (!s || chains_per_group < 1) { set_error("bdrt_sampler_rank_diagnostics: bad arguments"); return -1; }
+    Sampler &S = s->impl;
+    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || (unit_hi - unit_lo) % chains_per_group || S.np.n_draws < 1) {
+        set_error("bdrt_sampler_rank_diagnostics: bad unit range");
+        return -1;
+    }
+    BDRT_HIP(hipSetDevice(S.prob->device));
+    BDRT_HIP(hipStreamSynchronize(S.stream));
+    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
+    return rank_diagnostics_to_host(dX, (long)S.np.n_draws * S.D, (long)S.D, S.prob->is_pos.data(),
+                                    (unit_hi - unit_lo) / chains_per_group, chains_per_group, S.np.n_draws, S.D, p_lo, p_hi, rhat,
+                                    ess_bulk, ess_tail, ess_mean, sd, S.stream);
+}
+
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s)
 {
     if (!s) return nullptr;

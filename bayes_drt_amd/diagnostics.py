@@ -1,4 +1,5 @@
-"""pystan-style HMC diagnostics of a sampling fit: `summary`, `stansummary`, `check_hmc_diagnostics`.
+"""HMC diagnostics of a sampling fit: pystan's `summary`, `stansummary`, `check_hmc_diagnostics`, and the rank-normalised
+`rank_diagnostics`, `sampler_rank_diagnostics`, `rank_summary`.
 
 The reference's users read these after every `fit(mode='sample')`: pystan 2.19's `sampling()` checked every run itself and
 logged the result (`WARNING:pystan:Rhat above 1.1 ...`), and its `fit.summary()` reported n_eff and Rhat.  Here the reductions
@@ -12,11 +13,19 @@ parameters of its parallel blocks (Y_hat*, Z_hat_p*, x_sum*) and its generated q
 (`SavedFit`) has the arrays it stored, plus Z_hat_re / Z_hat_im / dups, which follow from them (not q: that needs the
 differentiation matrices).
 
+Rank-normalised diagnostics (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; bdrt_rank.hip, definitions written out in
+tests/rank_numpy.py): `rank_diagnostics` on host draws, `sampler_rank_diagnostics` / `Sampler.rank_diagnostics` on a sampler's
+device draws, `rank_summary` (also `StanFit.rank_summary`, `SavedFit.rank_summary`) for the columns of a fit, and the checks
+'rank_Rhat', 'ess_bulk', 'ess_tail' (`RANK_CHECKS`) of `check_hmc_diagnostics`, which run only when asked for: the automatic
+check after `fit` / `fit_many` is pystan's, unchanged.  The convention (everything on split chains) is that of Stan's
+`posterior` package and of arviz; neither was available to compare against, so no bit-parity with them is claimed.
+
 Comparing fits (PSIS-LOO, WAIC, the Pareto k-hat of every observation) is in bayes_drt_amd.loo; its relative efficiency
 comes from `column_diagnostics` here.
 
 Out of scope: pystan's E-BFMI check ('energy').  It needs the Hamiltonian of every draw, and no sampler kernel records it;
-`checks=['energy']` raises NotImplementedError.
+`checks=['energy']` raises NotImplementedError.  Of the rank-normalised family: the MCSE of sd and of quantiles, rank plots,
+the sharded path of parallel.py, and making these checks the default of `fit` / `fit_many`.
 """
 import ctypes as C
 import logging
@@ -30,6 +39,11 @@ logger = logging.getLogger('bayes_drt_amd')
 MAX_FLAT = 1000                                  # pystan's sampling(): above this many flat names, n_eff / Rhat are skipped
 DEFAULT_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)
 CHECKS = ('n_eff', 'Rhat', 'divergence', 'treedepth')
+RANK_CHECKS = ('rank_Rhat', 'ess_bulk', 'ess_tail')    # on request only: check_hmc_diagnostics(fit, checks=[...])
+RANK_PROBS = (0.05, 0.5, 0.95)
+TAIL_PROBS = (0.05, 0.95)
+RANK_RHAT_MAX = 1.01                             # thresholds of Vehtari et al. 2021
+ESS_PER_CHAIN_MIN = 100.0
 
 
 # ---------------------------------------------------------------------------------------------------- declarations
@@ -209,9 +223,97 @@ def sampler_diagnostics(sampler, unit_lo, unit_hi, chains):
     return tuple(out)
 
 
+def _tail_probs(tail_probs, who):
+    try:
+        p_lo, p_hi = (float(p) for p in tail_probs)
+    except (TypeError, ValueError):
+        raise ValueError('%s: tail_probs must be two probabilities (p_lo, p_hi)' % who)
+    if not (0.0 < p_lo < 1.0 and 0.0 < p_hi < 1.0) or not p_lo < p_hi:
+        raise ValueError('%s: tail_probs need 0 < p_lo < p_hi < 1, got (%g, %g)' % (who, p_lo, p_hi))
+    return p_lo, p_hi
+
+
+def _rank_shape(who, chains, draws):
+    """Checks that need no GPU: the split draws 2 * chains * (draws // 2) of one column must fit the kernel's LDS."""
+    if chains < 1 or chains > 64:
+        raise ValueError('%s: %d chains (1 ... 64)' % (who, chains))
+    if draws < 2:
+        raise ValueError('%s: %d draws per chain, the split chains need at least 2' % (who, draws))
+    limit = _lib.load_library().bdrt_rank_max_draws()
+    if 2 * chains * (draws // 2) > limit:
+        raise ValueError('%s: %d split draws per column, the kernel holds at most %d' % (who, 2 * chains * (draws // 2), limit))
+
+
+def _rank_dict(rhat, bulk, tail, essm, sd):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mcse = sd / np.sqrt(essm)
+    return {'rhat': rhat, 'ess_bulk': bulk, 'ess_tail': tail, 'ess_mean': essm, 'mcse_mean': mcse, 'sd': sd}
+
+
+def rank_diagnostics(X, chains, is_pos=None, tail_probs=TAIL_PROBS):
+    """Rank-normalised diagnostics of X [G groups, chains * draws, C columns] (or [chains * draws, C]: G = 1) on the GPU: dict of
+    'rhat' (rank-normalised, folded split R-hat), 'ess_bulk', 'ess_tail' (the smaller ESS of the indicators of the two
+    `tail_probs` quantiles), 'ess_mean', 'mcse_mean', 'sd', each [G, C] (or [C]).  Definitions: tests/rank_numpy.py.  All on
+    the split chains: an odd number of draws per chain drops the middle draw, of 'sd' too.  ValueError when the draws do not
+    split into the chains, for tail probabilities outside 0 < p_lo < p_hi < 1, and when one column has more split draws than
+    the kernel holds in LDS (bdrt_rank_max_draws(): 8192, i.e. 8 chains x 1000 or 4 x 2000)."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+    one = X.ndim == 2
+    if one:
+        X = X[None]
+    if X.ndim != 3:
+        raise ValueError('rank_diagnostics: X must be [G, chains * draws, C] or [chains * draws, C]')
+    G, rows, Cn = X.shape
+    chains = int(chains)
+    if chains < 1 or rows % chains:
+        raise ValueError('rank_diagnostics: %d draws do not split into %d chains' % (rows, chains))
+    p_lo, p_hi = _tail_probs(tail_probs, 'rank_diagnostics')
+    _rank_shape('rank_diagnostics', chains, rows // chains)
+    mask = None
+    if is_pos is not None:
+        mask = np.ascontiguousarray(np.asarray(is_pos, dtype=np.uint8))
+        if mask.shape != (Cn,):
+            raise ValueError('rank_diagnostics: is_pos must have one flag per column')
+    lib = _lib.require_gpu()
+    out = [np.empty((G, Cn)) for _ in range(5)]
+    if G and Cn:
+        _lib.check(lib.bdrt_rank_diagnostics(_lib.ptr(X), G, chains, rows // chains, Cn, Cn, _lib.ptr(mask), p_lo, p_hi,
+                                             *[_lib.ptr(o) for o in out]), 'bdrt_rank_diagnostics')
+    return _rank_dict(*[(o[0] if one else o) for o in out])
+
+
+def sampler_rank_diagnostics(sampler, unit_lo, unit_hi, chains, tail_probs=TAIL_PROBS):
+    """`rank_diagnostics` [G x D] of the constrained parameters over the draws a sampler holds in HBM (units [unit_lo, unit_hi),
+    `chains` consecutive units per group): one launch, no copy of the draws."""
+    chains = int(chains)
+    if chains < 1 or unit_hi <= unit_lo or (unit_hi - unit_lo) % chains:
+        raise ValueError('sampler_rank_diagnostics: units [%d, %d) do not split into groups of %d chains' % (unit_lo, unit_hi, chains))
+    p_lo, p_hi = _tail_probs(tail_probs, 'sampler_rank_diagnostics')
+    _rank_shape('sampler_rank_diagnostics', chains, int(sampler.n_draws))
+    G = (unit_hi - unit_lo) // chains
+    D = sampler.problem.D
+    out = [np.empty((G, D)) for _ in range(5)]
+    _lib.check(sampler._lib.bdrt_sampler_rank_diagnostics(sampler.handle, int(unit_lo), int(unit_hi), chains, p_lo, p_hi,
+                                                          *[_lib.ptr(o) for o in out]), 'bdrt_sampler_rank_diagnostics')
+    return _rank_dict(*out)
+
+
 # ---------------------------------------------------------------------------------------------------- summary
 def _quantile_names(probs):
     return ['{:g}%'.format(100 * p) for p in probs]
+
+
+def _stacked_columns(fit, pars, who):
+    """(flat names, X [chains * draws, n_flat]) of the columns of a fit, or of the parameters `pars` among them."""
+    cols = fit_columns(fit)
+    if pars is not None:
+        want = [pars] if isinstance(pars, str) else list(pars)
+        unknown = [p for p in want if p not in {c[0] for c in cols}]
+        if unknown:
+            raise ValueError('%s: unknown parameter(s) %s' % (who, unknown))
+        cols = [c for c in cols if c[0] in want]
+    names = [n for nm, a, sc in cols for n in flatnames(nm, a.shape[1], sc)]
+    return names, np.hstack([a for _, a, _ in cols])
 
 
 def summary(fit, pars=None, probs=DEFAULT_PROBS):
@@ -220,15 +322,7 @@ def summary(fit, pars=None, probs=DEFAULT_PROBS):
     quantiles), 'c_summary_rownames', 'c_summary_colnames'.  Quantiles: numpy's 'linear' rule (bdrt_percentiles)."""
     from . import post
     probs = tuple(float(p) for p in probs)
-    cols = fit_columns(fit)
-    if pars is not None:
-        want = [pars] if isinstance(pars, str) else list(pars)
-        unknown = [p for p in want if p not in {c[0] for c in cols}]
-        if unknown:
-            raise ValueError('summary: unknown parameter(s) %s' % unknown)
-        cols = [c for c in cols if c[0] in want]
-    names = [n for nm, a, sc in cols for n in flatnames(nm, a.shape[1], sc)]
-    X = np.hstack([a for _, a, _ in cols])
+    names, X = _stacked_columns(fit, pars, 'summary')
     M, N = fit.chains, fit.n_draws
     mean, sd, n_eff, rhat = column_diagnostics(X, M)
     q = np.asarray(probs) * 100.0
@@ -246,6 +340,24 @@ def summary(fit, pars=None, probs=DEFAULT_PROBS):
     return {'summary': S, 'summary_rownames': np.array(names), 'summary_colnames': tuple(['mean', 'se_mean', 'sd'] + qn +
                                                                                           ['n_eff', 'Rhat']),
             'c_summary': cs, 'c_summary_rownames': np.array(names), 'c_summary_colnames': tuple(['mean', 'sd'] + qn)}
+
+
+def rank_summary(fit, pars=None, probs=RANK_PROBS, tail_probs=TAIL_PROBS):
+    """The table of `summary` with the diagnostics of Vehtari et al. 2021 in place of pystan's: dict with 'summary' [n_flat x
+    (6 + len(probs))] (mean, mcse_mean, sd, quantiles, ess_bulk, ess_tail, Rhat), 'summary_rownames' (the rows of `summary`),
+    'summary_colnames'.  Rhat is the rank-normalised, folded split R-hat (`rank_diagnostics`); mcse_mean = sd / sqrt(ess_mean);
+    sd is that of the split chains.  Quantiles: numpy's 'linear' rule (bdrt_percentiles).  ess_tail is the ESS behind the
+    `tail_probs` quantiles: tail_probs=(0.025, 0.975) gives the effective number of draws behind the package's own 95 % bands
+    (`predict_distribution(percentile=)`, `coef_percentile`, `predict_Z(percentile=)`)."""
+    from . import post
+    probs = tuple(float(p) for p in probs)
+    names, X = _stacked_columns(fit, pars, 'rank_summary')
+    r = rank_diagnostics(X, fit.chains, tail_probs=tail_probs)
+    mean = column_diagnostics(X, fit.chains)[0]
+    pct = post.percentile(X, np.asarray(probs) * 100.0, axis=0).reshape(len(probs), X.shape[1])
+    S = np.column_stack([mean, r['mcse_mean'], r['sd'], pct.T, r['ess_bulk'], r['ess_tail'], r['rhat']])
+    return {'summary': S, 'summary_rownames': np.array(names),
+            'summary_colnames': tuple(['mean', 'mcse_mean', 'sd'] + _quantile_names(probs) + ['ess_bulk', 'ess_tail', 'Rhat'])}
 
 
 def stansummary(fit, pars=None, probs=DEFAULT_PROBS, digits_summary=2):
@@ -286,6 +398,9 @@ def treedepth_message(n_max, n_total, max_treedepth=10):
 
 RHAT_MESSAGE = 'Rhat above 1.1 or below 0.9 indicates that the chains very likely have not mixed'
 NEFF_MESSAGE = 'n_eff / iter below 0.001 indicates that the effective sample size has likely been overestimated'
+RANK_RHAT_MESSAGE = 'Rank-normalised Rhat above 1.01 indicates that the chains have not mixed'
+ESS_BULK_MESSAGE = 'Bulk ESS below 100 per chain indicates that posterior means and medians may be unreliable'
+ESS_TAIL_MESSAGE = 'Tail ESS below 100 per chain indicates that posterior variances and tail quantiles may be unreliable'
 SKIP_MESSAGE = ('Maximum (flat) parameter count ({}) exceeded: skipping diagnostic tests for n_eff and Rhat.\n'
                 'To run all diagnostics call bayes_drt_amd.diagnostics.check_hmc_diagnostics(fit)').format(MAX_FLAT)
 
@@ -302,16 +417,18 @@ def _checks_arg(checks):
     if 'energy' in checks:
         raise NotImplementedError("the E-BFMI check ('energy') needs the Hamiltonian of every draw, which no sampler kernel "
                                   "records; the other checks are %s" % (CHECKS,))
-    bad = [c for c in checks if c not in CHECKS]
+    bad = [c for c in checks if c not in CHECKS + RANK_CHECKS]
     if bad:
         raise ValueError('unknown check(s) %s' % bad)
     return checks
 
 
 def report(n_eff, rhat, total_draws, chain_div, chain_treedepth, adapt_delta=0.9, max_treedepth=10, checks=None, verbose=True,
-           per_chain=False, prefix=''):
+           per_chain=False, prefix='', rank_rhat=None, ess_bulk=None, ess_tail=None):
     """Log pystan's lines for precomputed values and return {check: passed}.  n_eff / rhat: flat arrays (may be None when the
-    check is not requested); chain_div / chain_treedepth: per-chain counts."""
+    check is not requested); chain_div / chain_treedepth: per-chain counts.  rank_rhat / ess_bulk / ess_tail: flat arrays for
+    the checks of RANK_CHECKS, which run only when `checks` names them: 'rank_Rhat' fails when a value is > 1.01 or NaN, the
+    ESS checks when a value is below 100 x chains or NaN."""
     checks = _checks_arg(checks)
     out = {}
     n_chains = len(chain_div)
@@ -356,6 +473,23 @@ def report(n_eff, rhat, total_draws, chain_div, chain_treedepth, adapt_delta=0.9
         elif verbose:
             logger.info(prefix + 'No iterations saturated the maximum tree depth of {}.'.format(max_treedepth))
         out['treedepth'] = n == 0
+    if 'rank_Rhat' in checks:
+        r = np.asarray(rank_rhat, dtype=float)
+        ok = not bool(np.any(np.isnan(r) | (r > RANK_RHAT_MAX)))
+        if not ok:
+            logger.warning(prefix + RANK_RHAT_MESSAGE)
+        elif verbose:
+            logger.info(prefix + 'Rank-normalised Rhat looks reasonable for all parameters')
+        out['rank_Rhat'] = ok
+    for name, vals, msg in (('ess_bulk', ess_bulk, ESS_BULK_MESSAGE), ('ess_tail', ess_tail, ESS_TAIL_MESSAGE)):
+        if name in checks:
+            e = np.asarray(vals, dtype=float)
+            ok = not bool(np.any(np.isnan(e) | (e < ESS_PER_CHAIN_MIN * n_chains)))
+            if not ok:
+                logger.warning(prefix + msg)
+            elif verbose:
+                logger.info(prefix + '%s ESS looks reasonable for all parameters' % ('Bulk' if name == 'ess_bulk' else 'Tail'))
+            out[name] = ok
     return out
 
 
@@ -363,16 +497,23 @@ def check_hmc_diagnostics(fit, pars=None, verbose=True, per_chain=False, checks=
     """pystan.check_hmc_diagnostics: {'n_eff', 'Rhat', 'divergence', 'treedepth'} -> bool, pystan's wording logged at WARNING
     to logging.getLogger('bayes_drt_amd') (verbose: the all-clear lines at INFO).  n_eff fails when n_eff / total draws <
     0.001 for some column; Rhat when some Rhat is > 1.1, < 0.9, NaN or inf.  Divergence and tree-depth counts are the
-    sampler's per-chain counters.  The E-BFMI check ('energy') is not available (module docstring)."""
+    sampler's per-chain counters.  The E-BFMI check ('energy') is not available (module docstring).
+    `checks` may also name 'rank_Rhat', 'ess_bulk' and 'ess_tail' (RANK_CHECKS; never part of the default): the thresholds of
+    Vehtari et al. 2021 on the values of `rank_summary` -- rank-normalised Rhat > 1.01 or NaN fails, bulk / tail ESS below
+    100 x chains or NaN fails."""
     checks = _checks_arg(checks)
     n_eff = rhat = None
     if 'n_eff' in checks or 'Rhat' in checks:
         s = summary(fit, pars)
         n_eff, rhat = s['summary'][:, -2], s['summary'][:, -1]
+    rank = {}
+    if any(c in RANK_CHECKS for c in checks):
+        rs = rank_summary(fit, pars)['summary']
+        rank = dict(rank_rhat=rs[:, -1], ess_bulk=rs[:, -3], ess_tail=rs[:, -2])
     diag = fit.diagnostics
     ad, td = _control(fit)
     return report(n_eff, rhat, fit.chains * fit.n_draws, [d['n_divergent'] for d in diag], [d['n_max_treedepth'] for d in diag],
-                  ad, td, checks, verbose, per_chain)
+                  ad, td, checks, verbose, per_chain, **rank)
 
 
 def auto_check(fit, flat_count, prefix='', n_eff=None, rhat=None):

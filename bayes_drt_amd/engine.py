@@ -145,6 +145,11 @@ class StanFit:
         from . import diagnostics
         return diagnostics.stansummary(self, pars, probs, digits_summary)
 
+    def rank_summary(self, pars=None, probs=(0.05, 0.5, 0.95), tail_probs=(0.05, 0.95)):
+        """Rank-normalised R-hat, bulk and tail ESS of every column (bayes_drt_amd.diagnostics.rank_summary)."""
+        from . import diagnostics
+        return diagnostics.rank_summary(self, pars, probs, tail_probs)
+
 
 class SavedFit(dict):
     """HMC result restored from a file: the same `fit[name]` / `chain_draws` / diagnostics surface as StanFit, backed by
@@ -176,6 +181,11 @@ class SavedFit(dict):
     def stansummary(self, pars=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digits_summary=2):
         from . import diagnostics
         return diagnostics.stansummary(self, pars, probs, digits_summary)
+
+    def rank_summary(self, pars=None, probs=(0.05, 0.5, 0.95), tail_probs=(0.05, 0.95)):
+        """The same over the stored arrays (bayes_drt_amd.diagnostics.rank_summary)."""
+        from . import diagnostics
+        return diagnostics.rank_summary(self, pars, probs, tail_probs)
 
     def __reduce__(self):
         return (SavedFit, (dict(self), self.chains, self.n_draws, self.diagnostics, self.theta))
@@ -526,6 +536,12 @@ class Sampler:
         `chains` consecutive units, reduced in HBM in one launch (bdrt_sampler_diagnostics)."""
         from .diagnostics import sampler_diagnostics
         return sampler_diagnostics(self, unit_lo, unit_hi, chains)
+
+    def rank_diagnostics(self, unit_lo, unit_hi, chains, tail_probs=(0.05, 0.95)):
+        """Rank-normalised R-hat, bulk / tail / mean ESS, MCSE and sd [G x D] of the same draws, as a dict, reduced in HBM in one
+        launch (bdrt_sampler_rank_diagnostics)."""
+        from .diagnostics import sampler_rank_diagnostics
+        return sampler_rank_diagnostics(self, unit_lo, unit_hi, chains, tail_probs)
 
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""

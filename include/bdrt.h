@@ -337,6 +337,21 @@ int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
  * is_pos[C] flags the exp() columns (NULL: none); outputs [G x C].  M <= 64. */
 int bdrt_diagnostics(const double *X, int G, int M, int N, int C, long ldx, const unsigned char *is_pos, double *mean,
                      double *sd, double *n_eff, double *rhat);
+/* Rank-normalised diagnostics (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; definitions: tests/rank_numpy.py), all on
+ * the SPLIT chains Y: chain m gives rows 2m (its first n = N / 2 draws) and 2m + 1 (its last n; an odd N drops the middle
+ * draw).  Per column: rhat, the larger of the plain R-hat over the 2M rows of the rank-normalised draws z and of the
+ * rank-normalised folded draws |Y - median|; ess_bulk, Geyer's ESS (as n_eff above, 2M chains of n draws) of z; ess_tail, the
+ * smaller ESS of the indicators 1[Y <= q], q the p_lo and p_hi quantiles of Y (numpy's linear rule); ess_mean, the ESS of Y;
+ * sd of Y (ddof = 1).  Every ESS is capped at S log10 S, S = 2M n.  A column with a non-finite draw, or whose draws are all
+ * equal, gives NaN in all five; n < 4 gives NaN ESS, n < 2 NaN rhat; a constant indicator series gives ess_tail = NaN.
+ * Outputs [G x C] (any may be NULL).  M <= 64, N >= 2, 0 < p_lo < p_hi < 1 and S <= bdrt_rank_max_draws() (8192), else -1.
+ * Bit-reproducible, and a column's results do not depend on what else is in the launch.  Layouts as bdrt_diagnostics /
+ * bdrt_sampler_diagnostics; the sampler's draws are not copied to the host. */
+int bdrt_rank_diagnostics(const double *X, int G, int M, int N, int C, long ldx, const unsigned char *is_pos, double p_lo,
+                          double p_hi, double *rhat, double *ess_bulk, double *ess_tail, double *ess_mean, double *sd);
+int bdrt_sampler_rank_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, double p_lo, double p_hi,
+                                  double *rhat, double *ess_bulk, double *ess_tail, double *ess_mean, double *sd);
+int bdrt_rank_max_draws(void);
 /* Model comparison of sampling fits: PSIS-LOO (Vehtari, Gelman, Gabry 2017) and WAIC; definitions: tests/psis_numpy.py.
  * Pointwise log-likelihood of `Z ~ normal(Z_hat, sigma_tot)`: Zhat, sig [G][S][N2] and z [G][N2] on the host (G fits, S draws,
  * N2 = 2 Nf scalar observations).  pair = 0: ll_out [G][S][N2]; pair = 1: ll_out [G][S][N2 / 2], column i = columns i and
@@ -373,6 +388,11 @@ const char *bdrt_version(void);
 int bdrt_debug_hessian_lin(bdrt_problem *p, const double *theta, int spec, int lin, double *H_out, double *held_out);
 /* the same with lin = 0 */
 int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H_out);
+/* A series of one column y [M][N] (host) as bdrt_rank_diagnostics forms it, z_out [2M][N / 2] in time order.  what = 0: the
+ * rank-normalised split draws z; 1: the z of the folded split draws (both NaN for a column that gives NaN); 2: the split
+ * draws themselves as the kernel stages them, i.e. exp(y) when is_pos != 0 (the device's exp, which may differ from the
+ * host's in the last bit). */
+int bdrt_debug_rank_z(const double *y, int M, int N, int is_pos, int what, double *z_out);
 
 #ifdef __cplusplus
 }
