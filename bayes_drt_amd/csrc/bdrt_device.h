@@ -22,6 +22,9 @@ constexpr int NC = 16;        // chains per workgroup = MFMA N
 // LDS the 16-chain sampler kernel keeps beside the evaluator's tile region (chain states, lp, spectrum ids ...): a problem is
 // accepted only if tile + this fits 160 KiB, so that whatever can be evaluated and optimised can also be sampled
 constexpr size_t SAMPLER_LDS_RESERVE = 6144;
+// P.w and P.Z are followed by this many readable doubles (bdrt_model.hip): the sampler's evaluator reads rows l32 + 32 v, v < 4, of a
+// spectrum without clamping them to nf (bdrt_tile_s1.h: load_spectrum), and P.Z holds less than 2 GiB (a 32-bit lane offset)
+constexpr int SPEC_PAD = 128;
 constexpr int NT = 512;       // threads per workgroup
 constexpr int NW = NT / 64;   // waves per workgroup
 constexpr int NG = NT / NC;   // row groups in the element-wise phases
@@ -386,6 +389,7 @@ struct TileIO {
     double *sigma_tot;
     double *params;        // optional [chain][D] constrained parameters
     long long *prof;       // optional cycle counters per phase (thread 0 of the workgroup), slots 0..9
+    int zoff;              // the sampler's S1 tile (LDSIO) only: byte offset of this lane's chain's spectrum in P.Z (spec * 2 nf * 8)
 };
 
 constexpr int UK = 6;      // elements per thread handled per unrolled batch in the K-loops  (K <= 192 -> one batch)

@@ -349,7 +349,7 @@ static int build_problem(Problem &P, const bdrt_dat *dat)
             if ((rc = upload(P, ld, &B.Ld)) || (rc = upload(P, lt, &B.Lt))) return rc;
         }
     }
-    std::vector<double> w(nf);
+    std::vector<double> w((size_t)nf + SPEC_PAD, 0.0);           // (padded: the sampler's spectrum request does not clamp its rows)
     for (int n = 0; n < nf; ++n) w[n] = 2.0 * M_PI * dat->freq[n];
     int rc;
     if ((rc = upload(P, w, &D.w))) return rc;
@@ -361,9 +361,13 @@ static int build_problem(Problem &P, const bdrt_dat *dat)
 static int set_Z(Problem &P, const double *Z, int n_spectra)
 {
     const size_t need = (size_t)n_spectra * 2 * P.dev.nf;
+    // the sampler addresses a chain's spectrum by a 32-bit byte offset and reads up to SPEC_PAD doubles beyond a row's end
+    if ((need + SPEC_PAD) * sizeof(double) >= ((size_t)1 << 31)) { set_error("spectra of one problem must stay below 2 GiB (%d given)", n_spectra); return -1; }
     if (need > P.z_capacity) {
         if (P.d_Z) hipFree(P.d_Z);
-        BDRT_HIP(hipMalloc((void **)&P.d_Z, need * sizeof(double)));
+        P.d_Z = nullptr; P.z_capacity = 0;
+        BDRT_HIP(hipMalloc((void **)&P.d_Z, (need + SPEC_PAD) * sizeof(double)));
+        BDRT_HIP(hipMemset(P.d_Z + need, 0, SPEC_PAD * sizeof(double)));
         P.z_capacity = need;
     }
     BDRT_HIP(hipMemcpy(P.d_Z, Z, need * sizeof(double), hipMemcpyHostToDevice));

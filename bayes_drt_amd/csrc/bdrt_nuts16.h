@@ -78,6 +78,9 @@ __device__ __forceinline__ void lds_wave_sync()
 #ifndef BDRT_KARG_RELOAD
 #define BDRT_KARG_RELOAD 1
 #endif
+#ifndef BDRT_FLAGS_BALLOT
+#define BDRT_FLAGS_BALLOT 1          // FREE_RUN: a lane reads ONE activity flag behind B1, one compare at the round's end (0: every lane ORs all 16)
+#endif
 #ifndef BDRT_NUTS_EARLY_STATE
 #define BDRT_NUTS_EARLY_STATE 1
 #endif
@@ -110,7 +113,9 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
     double *hvk = lpn + NC;             // wide-vector path: [NC][2] results of a chain's own pass handed to the cooperative phase
     ChainState *sts = reinterpret_cast<ChainState *>(hvk + 2 * NC);
     int *spec = reinterpret_cast<int *>(sts + NC);
-    volatile int *slow = spec + NC;     // round stamp (round + 1) of the last round in which some chain did something long (see stage Z)
+    // (an LDS pointer by type: through a generic one the stamp is written and read with flat instructions)
+    typedef volatile __attribute__((address_space(3))) int *lds_vint;
+    lds_vint slow = (lds_vint)(spec + NC);     // round stamp (round + 1) of the last round in which some chain did something long (see stage Z)
     int *thoff = spec + NC + 4;         // wide-vector path: offset of each chain's live theta row (0 or V_TH2 - V_TH rows)
     int *hvy = thoff + NC;              // wide-vector path: chains that the cooperative phase finishes (bdrt_nuts_wide.h)
     double *ublk = reinterpret_cast<double *>(hvy + NC);     // register path: [NC][16] uniforms of sixteen consecutive leaves (stage S1)
@@ -148,6 +153,7 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
     }
     io.lp = lpn;
     io.spec = spec;
+    io.zoff = MODE == 2 ? spec[c] * (2 * P.nf * (int)sizeof(double)) : 0;      // (below 2 GiB: bdrt_model.hip set_Z)
     io.nvalid = NC;            // padded columns carry a DONE state and finite vectors
     io.jacobian = 1;
     io.Z_hat = nullptr; io.sigma_tot = nullptr; io.params = nullptr;
@@ -285,9 +291,14 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
             }
         };
         int any_next = 0;
+        int flag_l = 0;                                    // BDRT_FLAGS_BALLOT: the flag of chain l32 & 15, as read behind B1
         if (MODE == 2) {
             auto read_flags = [&]() {
-                if constexpr (FREE_RUN) {
+                if constexpr (FREE_RUN && BDRT_FLAGS_BALLOT) {
+                    // (one ds_read_b32 per lane here, nothing else inside the GEMM phase: 16 reads and 15 dependent ORs per lane came
+                    // to rest behind the forward GEMM's last MFMA, in front of B2)
+                    flag_l = ((const __attribute__((address_space(3))) int *)actf)[l32 & (NC - 1)];
+                } else if constexpr (FREE_RUN) {
                     typedef int iv4 __attribute__((ext_vector_type(4)));
                     typedef const __attribute__((address_space(3))) iv4 *lds_i4;
                     int v = 0;
@@ -1001,7 +1012,9 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
             const bool running = ph == PH_INIT || ph == PH_EPS || ph == PH_TREE;
             if constexpr (FREE_RUN) {
                 if (l32 == 0) actf[c] = running ? 1 : 0;
-                any_act = any_next;                         // (the same 16 flags were read by every thread after this round's first barrier)
+                // (the same 16 flags were read by every wave after this round's first barrier; all lanes are active here)
+                if constexpr (BDRT_FLAGS_BALLOT) any_next = __builtin_amdgcn_ballot_w64(flag_l != 0) != 0 ? 1 : 0;
+                any_act = any_next;
             } else {
                 any_act = __syncthreads_or(running);
             }

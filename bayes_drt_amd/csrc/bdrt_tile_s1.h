@@ -893,6 +893,12 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
 #ifndef BDRT_SPEC_EARLY
 #define BDRT_SPEC_EARLY 0
 #endif
+#ifndef BDRT_SPEC_GLOBAL
+#define BDRT_SPEC_GLOBAL 1               // LDSIO: the spectrum request as global loads at lane offset + immediate (0: flat loads, clamped rows)
+#endif
+#ifndef BDRT_EPI_LANE_BASE
+#define BDRT_EPI_LANE_BASE 1             // the epilogue's operand reads: one lane base per array, formed behind B4, + immediate offsets (0: per-row addresses, clamped)
+#endif
 #ifndef BDRT_EARLY_P2
 #define BDRT_EARLY_P2 1
 #endif
@@ -905,6 +911,21 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
     constexpr bool EARLY_P2 = BDRT_EARLY_P2 != 0;
     double zre_[UNV], zim_[UNV], wn_[UNV];
     auto load_spectrum = [&]() {
+        if constexpr (LDSIO && BDRT_SPEC_GLOBAL) {
+            // The sampler: nothing of the request but the lane's row changes from round to round, and even that only because l32 is
+            // opaque per call.  One lane offset for P.w, one (plus the chain's spectrum, TileIO::zoff) for both parts of P.Z; the rows
+            // n = l32 + LPC v are immediate offsets.  No clamp of n: P.w and P.Z are padded on the host (SPEC_PAD doubles behind the
+            // last spectrum), what is read beyond nf is never used.  Global, not flat, loads: a flat load counts on lgkmcnt as well,
+            // so the s_waitcnt lgkmcnt(0) in front of the next barrier would wait for the round trip to memory.
+            static_assert(LPC * UNV <= SPEC_PAD, "P.w / P.Z are padded by SPEC_PAD doubles");
+            typedef const __attribute__((address_space(1))) double *gptr;
+            typedef const __attribute__((address_space(1))) char *gbytes;
+            const unsigned l8 = 8u * (unsigned)l32, z8 = (unsigned)io.zoff + l8;
+            const gptr wl = (gptr)((gbytes)P.w + l8), zr = (gptr)((gbytes)P.Z + z8), zi = (gptr)((gbytes)(P.Z + nf) + z8);
+#pragma unroll
+            for (int v = 0; v < UNV; ++v) { zre_[v] = zr[LPC * v]; zim_[v] = zi[LPC * v]; wn_[v] = wl[LPC * v]; }
+            return;
+        }
         const int sp = io.spec ? io.spec[cc] : 0;
         const double *Zm = P.Z + (size_t)sp * N2;
 #pragma unroll
@@ -1204,10 +1225,23 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
     {
         // (all LDS reads of the phase in one batch: the rows of A^T g beyond K lie inside the tile, the private rows are 32 KU long)
         double ag_[UKV], gl2_[UKV];
+        if constexpr (BDRT_EPI_LANE_BASE) {
+            // One lane base per array, the rows k = l32 + LPC u at immediate offsets: swz's XOR term depends on k & 15 = l32 & 15 only.
+            // No clamp of k to K: what is read beyond K is dropped by the selects below, and the walk ends inside the private rows,
+            // which every S1 layout holds behind Xs and Zh (s1_lds_doubles).  The base is formed from a copy of l32 that is made
+            // behind B4: worked out of the round's l32 these addresses are scheduled in front of the barrier, into the GEMM's tail.
+            static_assert(LPC % 16 == 0 && LPC * UKV <= 2 * RW, "rows l32 + LPC u of Xs: same swizzle, inside the workgroup's LDS");
+            int le = l32;
+            __asm__ volatile("" : "+v"(le));
+            const double *xs0 = Xs + swz(le, c), *w0 = wrow + MAXBW + le, *x0 = xrow + MAXBW + le;
 #pragma unroll
-        for (int u = 0; u < UKV; ++u) {
-            const int k = l32 + LPC * u, kk = k < K ? k : 0;
-            ag_[u] = Xs[swz(kk, c)]; gl2_[u] = wrow[MAXBW + k]; gu_[u] = xrow[MAXBW + k];
+            for (int u = 0; u < UKV; ++u) { ag_[u] = xs0[LPC * NC * u]; gl2_[u] = w0[LPC * u]; gu_[u] = x0[LPC * u]; }
+        } else {
+#pragma unroll
+            for (int u = 0; u < UKV; ++u) {
+                const int k = l32 + LPC * u, kk = k < K ? k : 0;
+                ag_[u] = Xs[swz(kk, c)]; gl2_[u] = wrow[MAXBW + k]; gu_[u] = xrow[MAXBW + k];
+            }
         }
 #pragma unroll
         for (int u = 0; u < UKV; ++u) {
