@@ -13,16 +13,18 @@
 //   pass 2    centred sums of squares of chains, halves and the whole column; the staged series is centred in place
 //   pass 3    autocovariances in blocks of 64 lags (one lag per lane, the four waves split the draw range), chain-averaged;
 //             thread 0 walks Geyer's pairs of the block and the loop stops at the block where the positive sequence ends
-// Every sum has a fixed order, so results repeat bit for bit, and do not depend on TC or on staging.  This file is compiled
-// with -ffp-contract=off: the products that accumulate are explicit fma() calls, everything else is rounded separately.
+// Every sum has a fixed order, so results repeat bit for bit, and do not depend on TC or on staging (bdrt_stats.h: the
+// reductions, R-hat over rows and Geyer's sequence, shared with bdrt_rank.hip).
 #include <cmath>
 
 #include "bdrt_host.h"
+#include "bdrt_stats.h"
 
 namespace bdrt {
 
 constexpr int DG_NT = 256;                       // 4 waves
-constexpr int DG_LAGS = 64;                      // lags per block of pass 3 (one per lane)
+constexpr int DG_NW = DG_NT / 64;
+constexpr int DG_LAGS = STATS_LAGS;              // lags per block of pass 3 (one per lane)
 constexpr int DG_MAX_TC = 8;                     // adjacent columns per workgroup
 constexpr int DG_MAX_CHAINS = 64;
 constexpr size_t DG_STAGE_BYTES = 64 * 1024;     // two workgroups per CU
@@ -34,13 +36,6 @@ struct DiagArgs {
     int M, N, C, TC;
     double *mean, *sd, *neff, *rhat;             // [G x C] device
 };
-
-__device__ inline double dg_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <bool STAGED>
 __global__ __launch_bounds__(DG_NT) void diag_kernel(DiagArgs a)
@@ -93,13 +88,13 @@ __global__ __launch_bounds__(DG_NT) void diag_kernel(DiagArgs a)
                 if (t < n) s1 += v;
                 else if (t >= h2) s2 += v;
             }
-            s = dg_wave_sum(s); s1 = dg_wave_sum(s1); s2 = dg_wave_sum(s2);
+            s = wave_sum(s); s1 = wave_sum(s1); s2 = wave_sum(s2);
             if (lane == 0) { part[w * PW + 3 * m] = s; part[w * PW + 3 * m + 1] = s1; part[w * PW + 3 * m + 2] = s2; }
         }
         nonfinite = __syncthreads_or(nonfinite);
         differs = __syncthreads_or(differs);
         if (tid < 3 * M) {
-            const double tot = ((part[tid] + part[PW + tid]) + part[2 * PW + tid]) + part[3 * PW + tid];
+            const double tot = waves_sum<DG_NW>(part + tid, PW);
             const int m = tid / 3, k = tid - 3 * m;
             if (k == 0) { cs[m] = tot; cm[m] = tot / (double)N; }
             else hm[(k - 1) * M + m] = tot / (double)n;
@@ -126,111 +121,35 @@ __global__ __launch_bounds__(DG_NT) void diag_kernel(DiagArgs a)
                 else if (t >= h2) { const double f = v - mu2; q2 = fma(f, f, q2); }
                 if (STAGED) col[(size_t)m * N + t] = d;
             }
-            q = dg_wave_sum(q); q1 = dg_wave_sum(q1); q2 = dg_wave_sum(q2);
+            q = wave_sum(q); q1 = wave_sum(q1); q2 = wave_sum(q2);
             if (lane == 0) { part[w * PW + 3 * m] = q; part[w * PW + 3 * m + 1] = q1; part[w * PW + 3 * m + 2] = q2; }
         }
-        gq = dg_wave_sum(gq);
+        gq = wave_sum(gq);
         if (lane == 0) part[w * PW + 3 * M] = gq;
         __syncthreads();
         if (tid <= 3 * M) {
-            const double tot = ((part[tid] + part[PW + tid]) + part[2 * PW + tid]) + part[3 * PW + tid];
+            const double tot = waves_sum<DG_NW>(part + tid, PW);
             const int m = tid / 3, k = tid - 3 * m;
             if (tid == 3 * M) sc[1] = tot;
             else if (k == 0) cs[m] = tot;
             else hs[(k - 1) * M + m] = tot;
         }
         __syncthreads();
-        // ---- scalars: sd, split R-hat, the variances of n_eff
+        // ---- scalars: sd, split R-hat over the 2M halves
+        const bool ok = !nonfinite && differs;
         if (tid == 0) {
             const size_t o = (size_t)g * a.C + c;
             a.mean[o] = gmean;
             a.sd[o] = MN > 1 ? sqrt(sc[1] / (double)(MN - 1)) : NAN;
-            const bool ok = !nonfinite && differs;
-            double rh = NAN;
-            if (ok && n >= 2) {
-                const int H = 2 * M;
-                double hbar = 0.0, W = 0.0, B = 0.0;
-                for (int h = 0; h < H; ++h) hbar += hm[h];
-                hbar /= (double)H;
-                for (int h = 0; h < H; ++h) { const double d = hm[h] - hbar; B = fma(d, d, B); }
-                B = (double)n * (B / (double)(H - 1));
-                for (int h = 0; h < H; ++h) W += hs[h] / (double)(n - 1);
-                W /= (double)H;
-                rh = sqrt((B / W + (double)(n - 1)) / (double)n);
-            }
-            a.rhat[o] = rh;
-            double mean_var = 0.0;
-            for (int m = 0; m < M; ++m) mean_var += (cs[m] / (double)N) * (double)N / (double)(N - 1);
-            mean_var /= (double)M;
-            double var_plus = mean_var * (double)(N - 1) / (double)N;
-            if (M > 1) {
-                double mb = 0.0, vb = 0.0;
-                for (int m = 0; m < M; ++m) mb += cm[m];
-                mb /= (double)M;
-                for (int m = 0; m < M; ++m) { const double d = cm[m] - mb; vb = fma(d, d, vb); }
-                var_plus += vb / (double)(M - 1);
-            }
-            sc[2] = mean_var;
-            sc[3] = var_plus;
-            sc[4] = (ok && N >= 4) ? 1.0 : 0.0;
-            if (!(ok && N >= 4)) a.neff[o] = NAN;
+            a.rhat[o] = ok ? rhat_rows(2 * M, n, hm, hs) : NAN;
         }
+        // ---- pass 3: autocovariance blocks and Geyer's sequences; the streamed series is centred as it is read
+        double tau = NAN;
+        if (ok)
+            tau = geyer_tau<DG_NW>([&](int m, int t) -> double { return STAGED ? col[(size_t)m * N + t] : val(m, t) - cm[m]; }, M,
+                                   N, cm, cs, part, rho, sc + 2);
+        if (tid == 0) a.neff[(size_t)g * a.C + c] = (ok && N >= 4) ? (double)MN / tau : NAN;
         __syncthreads();
-        if (sc[4] == 0.0) { __syncthreads(); continue; }
-        // ---- pass 3: autocovariance blocks and Geyer's sequences (state in thread 0)
-        const double mean_var = sc[2], var_plus = sc[3];
-        const int chunk = (N + 3) / 4, tw0 = min(N, w * chunk), tw1 = min(N, tw0 + chunk);
-        double acc_pm = 0.0, prev_pm = 0.0;                           // thread 0: sum of monotone pair sums so far, last one
-        for (int k0 = 0;; k0 += DG_LAGS) {
-            const int k = k0 + lane;
-            double s = 0.0;
-            if (k < N) {
-                const int te = min(tw1, N - k);
-                for (int m = 0; m < M; ++m) {
-                    if (STAGED) {
-                        const double *cc = col + (size_t)m * N;
-                        for (int t = tw0; t < te; ++t) s = fma(cc[t], cc[t + k], s);
-                    } else {
-                        const double mu = cm[m];
-                        for (int t = tw0; t < te; ++t) s = fma(val(m, t) - mu, val(m, t + k) - mu, s);
-                    }
-                }
-            }
-            part[w * PW + lane] = s;
-            __syncthreads();
-            if (tid < DG_LAGS) {
-                const double S = ((part[tid] + part[PW + tid]) + part[2 * PW + tid]) + part[3 * PW + tid];
-                const double acov_mean = (S / (double)N) / (double)M;
-                rho[tid] = 1.0 - (mean_var - acov_mean) / var_plus;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double tau = NAN;
-                bool done = k0 + DG_LAGS >= N;                        // (never reached: the sequence stops before lag N - 2)
-                for (int l = 0; l < DG_LAGS && !(tau == tau); l += 2) {
-                    const int jp = (k0 + l) >> 1;                     // pair jp = lags (2 jp, 2 jp + 1)
-                    const double ev = jp == 0 ? 1.0 : rho[l], od = rho[l + 1];
-                    const bool cont = (2 * jp + 1 < N - 4) && (ev + od > 0.0);
-                    if (cont) {
-                        const double p = ev + od;
-                        const double pm = (jp == 0 || !(p > prev_pm)) ? p : prev_pm;
-                        acc_pm += pm;
-                        prev_pm = pm;
-                    } else {
-                        const double e = (jp == 0 || ev + od >= 0.0) ? ev : 0.0;
-                        const double b = ev > 0.0 ? ev : 0.0;
-                        tau = -1.0 + 2.0 * (acc_pm + e) + b;
-                    }
-                }
-                if (tau == tau) done = true;
-                if (done) a.neff[(size_t)g * a.C + c] = (double)MN / tau;
-                sc[5] = done ? 1.0 : 0.0;
-            }
-            __syncthreads();
-            const bool done = sc[5] != 0.0;
-            __syncthreads();
-            if (done) break;
-        }
     }
 }
 
@@ -259,8 +178,7 @@ int diagnostics_device(const double *dX, long unit_stride, long row_stride, cons
             return hipFuncSetAttribute((const void *)diag_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         }));
     const int tiles = (C + TC - 1) / TC;
-    for (int g0 = 0; g0 < G; g0 += 65535) {
-        const int gn = std::min(G - g0, 65535);
+    const int rc = for_grid_y_chunks(G, [&](int g0, int gn) {
         DiagArgs a;
         a.X = dX + (size_t)g0 * M * unit_stride;
         a.unit_stride = unit_stride; a.row_stride = row_stride; a.expcol = dExp;
@@ -269,8 +187,8 @@ int diagnostics_device(const double *dX, long unit_stride, long row_stride, cons
         a.mean = dMean + o; a.sd = dSd + o; a.neff = dNeff + o; a.rhat = dRhat + o;
         if (staged) hipLaunchKernelGGL(diag_kernel<true>, dim3(tiles, gn), dim3(DG_NT), lds, stream, a);
         else hipLaunchKernelGGL(diag_kernel<false>, dim3(tiles, gn), dim3(DG_NT), lds, stream, a);
-        BDRT_HIP(hipGetLastError());
-    }
+    });
+    if (rc) return rc;
     BDRT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
@@ -279,30 +197,16 @@ int diagnostics_device(const double *dX, long unit_stride, long row_stride, cons
 int diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M, int N,
                         int C, double *mean, double *sd, double *n_eff, double *rhat, hipStream_t stream)
 {
-    double *dOut = nullptr;
-    unsigned char *dExp = nullptr;
-    const size_t nb = (size_t)G * C * sizeof(double);
-    hipError_t e = hipMalloc((void **)&dOut, 4 * nb);
-    if (e == hipSuccess && is_pos) {
-        e = hipMalloc((void **)&dExp, (size_t)C);
-        if (e == hipSuccess) e = hipMemcpy(dExp, is_pos, (size_t)C, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        hipFree(dOut); hipFree(dExp);
-        set_error("bdrt diagnostics: %s", hipGetErrorString(e));
-        return -10;
-    }
     const size_t gc = (size_t)G * C;
-    int rc = diagnostics_device(dX, unit_stride, row_stride, dExp, G, M, N, C, dOut, dOut + gc, dOut + 2 * gc, dOut + 3 * gc,
-                                stream);
-    double *outs[4] = {mean, sd, n_eff, rhat};
-    for (int k = 0; k < 4 && rc == 0; ++k) {
-        if (!outs[k]) continue;
-        e = hipMemcpy(outs[k], dOut + k * gc, nb, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error("bdrt diagnostics: %s", hipGetErrorString(e)); rc = -10; }
-    }
-    hipFree(dOut); hipFree(dExp);
-    return rc;
+    DevBuf<double> dOut;
+    DevBuf<unsigned char> dExp;
+    BDRT_HIP(dOut.alloc(4 * gc));
+    if (is_pos && upload(dExp, is_pos, (size_t)C)) return -10;
+    const int rc = diagnostics_device(dX, unit_stride, row_stride, dExp, G, M, N, C, dOut, dOut + gc, dOut + 2 * gc, dOut + 3 * gc,
+                                      stream);
+    if (rc) return rc;
+    double *const outs[4] = {mean, sd, n_eff, rhat};
+    return download_planes(dOut, gc, outs, 4);
 }
 
 }  // namespace bdrt
@@ -316,13 +220,9 @@ int bdrt_diagnostics(const double *X, int G, int M, int N, int C, long ldx, cons
 {
     if (!X || G < 1 || M < 1 || N < 1 || C < 1 || ldx < C) { set_error("bdrt_diagnostics: bad arguments"); return -1; }
     bind_process_device();
-    double *dX = nullptr;
-    const size_t nb = ((size_t)G * M * N - 1) * ldx * sizeof(double) + (size_t)C * sizeof(double);
-    if (hipMalloc((void **)&dX, nb) != hipSuccess) { set_error("bdrt_diagnostics: hipMalloc(%zu) failed", nb); return -10; }
-    if (hipMemcpy(dX, X, nb, hipMemcpyHostToDevice) != hipSuccess) { hipFree(dX); set_error("bdrt_diagnostics: copy failed"); return -10; }
-    const int rc = diagnostics_to_host(dX, (long)N * ldx, ldx, is_pos, G, M, N, C, mean, sd, n_eff, rhat, nullptr);
-    hipFree(dX);
-    return rc;
+    DevBuf<double> dX;
+    if (upload_rows(dX, X, (size_t)G * M * N, ldx, C)) return -10;
+    return diagnostics_to_host(dX, (long)N * ldx, ldx, is_pos, G, M, N, C, mean, sd, n_eff, rhat, nullptr);
 }
 
 }  // extern "C"

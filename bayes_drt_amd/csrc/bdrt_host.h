@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -70,6 +71,41 @@ struct DevBuf {
     T *release() { T *q = p; p = nullptr; return q; }
     operator T *() const { return p; }
 };
+
+// host staging of the entry points that take host arrays: status 0 or -10, error text set
+// d <- a fresh device buffer holding the n elements at h
+template <class T>
+int upload(DevBuf<T> &d, const T *h, size_t n)
+{
+    BDRT_HIP(d.alloc(n));
+    BDRT_HIP(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// host draws of `rows` rows of C columns, leading dimension ld >= C: everything up to the last row's last column
+inline int upload_rows(DevBuf<double> &d, const double *X, size_t rows, long ld, int C)
+{
+    return upload(d, X, (rows - 1) * (size_t)ld + (size_t)C);
+}
+
+// k result planes of n elements each, adjacent on the device, to the host arrays outs[0 .. k); null outputs are skipped
+inline int download_planes(const double *d, size_t n, double *const *outs, int k)
+{
+    for (int i = 0; i < k; ++i)
+        if (outs[i]) BDRT_HIP(hipMemcpy(outs[i], d + (size_t)i * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// grid.y holds at most 65535 blocks: launch(g0, gn) for the chunks [g0, g0 + gn) of G groups, in order
+template <class F>
+int for_grid_y_chunks(int G, F launch)
+{
+    for (int g0 = 0; g0 < G; g0 += 65535) {
+        launch(g0, std::min(G - g0, 65535));
+        BDRT_HIP(hipGetLastError());
+    }
+    return 0;
+}
 
 struct Problem {
     DevProblem dev;                 // device view (pointers are device pointers), host copy

@@ -19,12 +19,13 @@
 //     7  smoothed tail values (stored behind y), the two tail sums; a tail element's ll is min(ll) minus its sorted x
 //        -> elpd_loo, pareto_k, n_tail
 // Every sum is a per-thread strided partial, a wave butterfly and the eight wave partials added in order; the compaction order
-// (the one thing atomics decide) is erased by the sort.  So a column gives the same bits alone or in any batch.  This file is
-// compiled with -ffp-contract=off: every product and sum is rounded separately, as in the numpy statement.
+// (the one thing atomics decide) is erased by the sort.  So a column gives the same bits alone or in any batch.  The reductions
+// and the sorting network are bdrt_stats.h's; every product and sum is rounded separately, as in the numpy statement.
 #include <cfloat>
 #include <cmath>
 
 #include "bdrt_host.h"
+#include "bdrt_stats.h"
 
 namespace bdrt {
 
@@ -93,45 +94,6 @@ struct LooArgs {
     int *ntail;
 };
 
-__device__ inline double lo_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ inline double lo_wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// block reductions in a fixed order: wave butterflies, then the eight wave results combined in order by every thread
-__device__ inline double lo_block_sum(double v, double *red)
-{
-    v = lo_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int i = 1; i < LO_NW; ++i) t += red[i];
-    return t;
-}
-
-__device__ inline double lo_block_max(double v, double *red)
-{
-    v = lo_wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int i = 1; i < LO_NW; ++i) t = fmax(t, red[i]);
-    return t;
-}
-
 // order-preserving key of a double (no NaN here): larger value <=> larger key
 __device__ inline unsigned long long lo_key(double v)
 {
@@ -188,21 +150,21 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
         if (tid == 0) { a.lpd[c] = NAN; a.elpd[c] = NAN; a.khat[c] = NAN; a.pwaic[c] = NAN; a.ntail[c] = 0; }
         return;
     }
-    mx = lo_block_max(mx, red);
-    mn = -lo_block_max(-mn, red);
+    mx = block_max<LO_NW>(mx, red);
+    mn = -block_max<LO_NW>(-mn, red);
     if (mx == mn) {                                                   // all draws equal: nothing to reweight
         if (tid == 0) { a.lpd[c] = mx; a.elpd[c] = mx; a.khat[c] = INFINITY; a.pwaic[c] = 0.0; a.ntail[c] = 0; }
         return;
     }
-    const double mean = lo_block_sum(sum, red) / (double)S;
+    const double mean = block_sum<LO_NW>(sum, red) / (double)S;
     double se = 0.0, sq = 0.0;
     for (int s = tid; s < S; s += LO_NT) {
         const double v = col[s], d = v - mean;
         se += exp(v - mx);
         sq = fma(d, d, sq);
     }
-    se = lo_block_sum(se, red);
-    sq = lo_block_sum(sq, red);
+    se = block_sum<LO_NW>(se, red);
+    sq = block_sum<LO_NW>(sq, red);
     if (tid == 0) {
         a.lpd[c] = (mx + log(se)) - a.log_S;
         a.pwaic[c] = sq / (double)(S - 1);
@@ -290,34 +252,14 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
             if (up && pos < a.cap) tail[pos] = x;
         }
     }
-    bden = lo_block_sum(bden, red);
-    bnum = lo_block_sum(bnum, red);                                   // (its barriers also publish tail[] and si[2])
+    bden = block_sum<LO_NW>(bden, red);
+    bnum = block_sum<LO_NW>(bnum, red);                                   // (its barriers also publish tail[] and si[2])
     const int n = min(si[2], a.cap);
     // ---- 5: sort the tail ascending; partners past the end are +inf and never move
-    int n2 = 1;
-    while (n2 < n) n2 <<= 1;
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int p = tid; p < (n2 >> 1); p += LO_NT) {
-                int i, q;
-                if (j == (k >> 1)) {
-                    const int blk = p / j, off = p - blk * j;
-                    i = blk * k + off;
-                    q = blk * k + (k - 1 - off);
-                } else {
-                    const int blk = p / j, off = p - blk * j;
-                    i = blk * 2 * j + off;
-                    q = i + j;
-                }
-                if (q < n) {
-                    const double u = tail[i], v = tail[q];
-                    if (u > v) { tail[i] = v; tail[q] = u; }
-                }
-            }
-        }
-    }
-    __syncthreads();
+    bitonic_any<LO_NT>(n, [&](int i, int q) {
+        const double u = tail[i], v = tail[q];
+        if (u > v) { tail[i] = v; tail[q] = u; }
+    });
     // ---- 6: generalised-Pareto fit to y = exp(tail) - exp(cutoff)
     double khat = INFINITY, sigma = NAN;
     double *y = col, *sm = col + a.cap;                               // 2 cap <= S for S >= 4; else n <= 4 and neither is used
@@ -337,7 +279,7 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
             const double nb = -bj[j];
             double s = 0.0;
             for (int r = lane; r < n; r += 64) s += log1p(nb * y[r]);
-            s = lo_wave_sum(s);
+            s = wave_sum(s);
             if (lane == 0) kj[j] = s / dn;
         }
         __syncthreads();
@@ -362,7 +304,7 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
         const double bp = sc[0];
         double s = 0.0;
         for (int r = tid; r < n; r += LO_NT) s += log1p(-bp * y[r]);
-        const double km = lo_block_sum(s, red) / dn;
+        const double km = block_sum<LO_NW>(s, red) / dn;
         sigma = -km / bp;
         khat = (dn * km + 5.0) / (dn + 10.0);
     }
@@ -380,8 +322,8 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
         mt = fmax(mt, v);
         ut = fmax(ut, v + (mn - t));
     }
-    mt = lo_block_max(mt, red);
-    ut = lo_block_max(ut, red);
+    mt = block_max<LO_NW>(mt, red);
+    ut = block_max<LO_NW>(ut, red);
     double tden = 0.0, tnum = 0.0;
     for (int r = tid; r < n; r += LO_NT) {
         const double t = tail[r];
@@ -389,8 +331,8 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
         tden += exp(v - mt);
         tnum += exp((v + (mn - t)) - ut);
     }
-    tden = lo_block_sum(tden, red);
-    tnum = lo_block_sum(tnum, red);
+    tden = block_sum<LO_NW>(tden, red);
+    tnum = block_sum<LO_NW>(tnum, red);
     if (tid == 0) {
         double lden, lnum;
         if (n == 0) {
@@ -441,24 +383,15 @@ int bdrt_pointwise_loglik(const double *Zhat, const double *sig, const double *z
     }
     bind_process_device();
     const size_t rows = (size_t)G * S, nin = rows * N2, nout = rows * (pair ? N2 / 2 : N2);
-    double *dZh = nullptr, *dSg = nullptr, *dz = nullptr, *dOut = nullptr;
-    auto cleanup = [&]() { hipFree(dZh); hipFree(dSg); hipFree(dz); hipFree(dOut); };
-#define LL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("bdrt_pointwise_loglik: %s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    LL_HIP(hipMalloc((void **)&dZh, nin * sizeof(double)));
-    LL_HIP(hipMalloc((void **)&dSg, nin * sizeof(double)));
-    LL_HIP(hipMalloc((void **)&dz, (size_t)G * N2 * sizeof(double)));
-    LL_HIP(hipMalloc((void **)&dOut, nout * sizeof(double)));
-    LL_HIP(hipMemcpy(dZh, Zhat, nin * sizeof(double), hipMemcpyHostToDevice));
-    LL_HIP(hipMemcpy(dSg, sig, nin * sizeof(double), hipMemcpyHostToDevice));
-    LL_HIP(hipMemcpy(dz, z, (size_t)G * N2 * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> dZh, dSg, dz, dOut;
+    if (upload(dZh, Zhat, nin) || upload(dSg, sig, nin) || upload(dz, z, (size_t)G * N2)) return -10;
+    BDRT_HIP(dOut.alloc(nout));
     const unsigned blocks = (unsigned)std::min<size_t>((nout + 255) / 256, 1u << 20);
-    hipLaunchKernelGGL(loglik_kernel, dim3(blocks), dim3(256), 0, nullptr, dZh, dSg, dz, rows, S, N2, pair,
-                       -0.5 * std::log(2.0 * M_PI), dOut);
-    LL_HIP(hipGetLastError());
-    LL_HIP(hipDeviceSynchronize());
-    LL_HIP(hipMemcpy(ll_out, dOut, nout * sizeof(double), hipMemcpyDeviceToHost));
-#undef LL_HIP
-    cleanup();
+    hipLaunchKernelGGL(loglik_kernel, dim3(blocks), dim3(256), 0, nullptr, (const double *)dZh, (const double *)dSg,
+                       (const double *)dz, rows, S, N2, pair, -0.5 * std::log(2.0 * M_PI), (double *)dOut);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipDeviceSynchronize());
+    BDRT_HIP(hipMemcpy(ll_out, dOut, nout * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -479,38 +412,33 @@ int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, dou
     bind_process_device();
     const int cap = (S + 4) / 5;
     const size_t lds = loo_lds_bytes(S, cap), nel = ncol * S;
-    double *dIn = nullptr, *dT = nullptr, *dOut = nullptr;
-    int *dM = nullptr;
-    auto cleanup = [&]() { hipFree(dIn); hipFree(dT); hipFree(dOut); hipFree(dM); };
-#define LO_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("bdrt_psis_loo: %s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    LO_HIP(hipMalloc((void **)&dIn, nel * sizeof(double)));
-    LO_HIP(hipMalloc((void **)&dT, nel * sizeof(double)));
-    LO_HIP(hipMalloc((void **)&dOut, 4 * ncol * sizeof(double)));
-    LO_HIP(hipMalloc((void **)&dM, 2 * ncol * sizeof(int)));
-    LO_HIP(hipMemcpy(dIn, ll, nel * sizeof(double), hipMemcpyHostToDevice));
-    LO_HIP(hipMemcpy(dM, M.data(), ncol * sizeof(int), hipMemcpyHostToDevice));
+    DevBuf<double> dIn, dT, dOut;
+    DevBuf<int> dM, dNtail;
+    if (upload(dIn, ll, nel) || upload(dM, M.data(), ncol)) return -10;
+    BDRT_HIP(dT.alloc(nel));
+    BDRT_HIP(dOut.alloc(4 * ncol));
+    BDRT_HIP(dNtail.alloc(ncol));
     const int tilesS = (S + LO_TILE - 1) / LO_TILE, tilesN = (N + LO_TILE - 1) / LO_TILE;
     const size_t tiles = (size_t)G * tilesS * tilesN;
-    if (tiles > 0x7fffffffull) { set_error("bdrt_psis_loo: too many tiles"); cleanup(); return -2; }
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, dIn, dT, S, N, tilesS, tilesN);
-    LO_HIP(hipGetLastError());
+    if (tiles > 0x7fffffffull) { set_error("bdrt_psis_loo: too many tiles"); return -2; }
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const double *)dIn, (double *)dT, S, N,
+                       tilesS, tilesN);
+    BDRT_HIP(hipGetLastError());
     static LdsAttrCache cache;
-    LO_HIP(cache.ensure(lds, [&]() {
+    BDRT_HIP(cache.ensure(lds, [&]() {
         return hipFuncSetAttribute((const void *)psis_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }));
     LooArgs a;
     a.T = dT; a.M = dM; a.S = S; a.cap = cap;
     a.log_dbl_min = std::log(DBL_MIN); a.log_S = std::log((double)S);
     a.lpd = dOut; a.elpd = dOut + ncol; a.khat = dOut + 2 * ncol; a.pwaic = dOut + 3 * ncol;
-    a.ntail = dM + ncol;
+    a.ntail = dNtail;
     hipLaunchKernelGGL(psis_kernel, dim3((unsigned)ncol), dim3(LO_NT), lds, nullptr, a);
-    LO_HIP(hipGetLastError());
-    LO_HIP(hipDeviceSynchronize());
-    double *outs[4] = {lpd, elpd_loo, pareto_k, p_waic};
-    for (int k = 0; k < 4; ++k) LO_HIP(hipMemcpy(outs[k], dOut + k * ncol, ncol * sizeof(double), hipMemcpyDeviceToHost));
-    LO_HIP(hipMemcpy(n_tail, dM + ncol, ncol * sizeof(int), hipMemcpyDeviceToHost));
-#undef LO_HIP
-    cleanup();
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipDeviceSynchronize());
+    double *const outs[4] = {lpd, elpd_loo, pareto_k, p_waic};
+    if (download_planes(dOut, ncol, outs, 4)) return -10;
+    BDRT_HIP(hipMemcpy(n_tail, dNtail, ncol * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 

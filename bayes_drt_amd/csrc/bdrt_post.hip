@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "bdrt_host.h"
+#include "bdrt_stats.h"
 
 namespace bdrt {
 
@@ -38,22 +39,6 @@ __global__ __launch_bounds__(64) void project_kernel(const double *__restrict__ 
         const int r = r0 + kq + 4 * q, m = m0 + col;
         if (r < rows && m < M) Y[(size_t)r * M + m] = acc[q] + (bias ? bias[m] : 0.0);
     }
-}
-
-// numpy.lib.function_base._lerp (numpy >= 1.22): a + (b - a) t, and b - (b - a)(1 - t) where t >= 0.5.
-// This file is compiled with -ffp-contract=off (Makefile): every product and sum is rounded separately, as in numpy's
-// element-wise ufuncs; a fused multiply-add would differ in the last bit.
-__device__ inline double numpy_lerp(double a, double b, double t)
-{
-    const double d = b - a;
-    const double dt = d * t;
-    double r = a + dt;
-    if (t >= 0.5) {
-        const double omt = 1.0 - t;
-        const double dm = d * omt;
-        r = b - dm;
-    }
-    return r;
 }
 
 // One workgroup per column.  IN_LDS: the column (padded to n2, a power of two) is sorted in LDS; otherwise (more than
@@ -107,17 +92,8 @@ __global__ __launch_bounds__(512) void percentile_kernel(const double *__restric
         }
     }
     for (int t = tid; t < nq; t += 512) {
-        // numpy: virtual index (n - 1) * (q / 100); previous = floor; gamma = virtual - previous; indexes clipped
-        const double quant = q[t];                       // already q / 100, divided on the host (IEEE division, as numpy)
-        const double virt = (double)(rows - 1) * quant;
-        double prev = floor(virt);
-        double gamma = virt - prev;
-        long lo = (long)prev, hi = lo + 1;
-        if (virt >= (double)(rows - 1)) { lo = rows - 1; hi = rows - 1; gamma = virt - prev; }
-        if (virt < 0.0) { lo = 0; hi = 0; }
-        lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
-        hi = hi < 0 ? 0 : (hi > rows - 1 ? rows - 1 : hi);
-        const double r = numpy_lerp(sh[lo], sh[hi], gamma);
+        // q[t] is already q / 100, divided on the host (IEEE division, as numpy's np.true_divide)
+        const double r = numpy_quantile([&](int i) -> double { return sh[i]; }, rows, q[t]);
         out[(size_t)t * ncols + col] = has_nan ? NAN : r;
     }
 }
@@ -140,14 +116,12 @@ static int launch_percentiles(const double *dY, int rows, long ld_row, int ncols
         return 0;
     }
     // long columns (np.percentile has no row limit): sort in a global scratch slice per column
-    double *work = nullptr;
-    BDRT_HIP(hipMalloc((void **)&work, (size_t)ncols * n2 * sizeof(double)));
+    DevBuf<double> work;
+    BDRT_HIP(work.alloc((size_t)ncols * n2));
     hipLaunchKernelGGL(percentile_kernel<false>, dim3(ncols), dim3(512), 512 * sizeof(double), stream, dY, rows, ld_row, 1L, ncols,
-                       n2, dq, nq, dOut, work, dExp, dMean);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    hipFree(work);
-    if (e != hipSuccess) { set_error("bdrt percentiles: %s", hipGetErrorString(e)); return -10; }
+                       n2, dq, nq, dOut, (double *)work, dExp, dMean);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -157,16 +131,12 @@ static int percentiles_dev(const double *dX, int rows, int K, long ldx, const do
 {
     if (rows < 1) { set_error("bdrt percentiles: no sample rows"); return -3; }
     if (dPhi) {
-        double *dY = nullptr;
-        BDRT_HIP(hipMalloc((void **)&dY, (size_t)rows * M * sizeof(double)));
+        DevBuf<double> dY;
+        BDRT_HIP(dY.alloc((size_t)rows * M));
         hipLaunchKernelGGL(project_kernel, dim3((rows + 15) / 16, (M + 15) / 16), dim3(64), 0, stream, dX, rows, K, ldx, dPhi,
-                           M, dBias, dY);
-        hipError_t e = hipGetLastError();
-        int rc = 0;
-        if (e != hipSuccess) { set_error("bdrt percentiles: %s", hipGetErrorString(e)); rc = -10; }
-        if (rc == 0) rc = launch_percentiles(dY, rows, (long)M, M, dq, nq, dOut, nullptr, dMean, stream);
-        hipFree(dY);
-        return rc;
+                           M, dBias, (double *)dY);
+        BDRT_HIP(hipGetLastError());
+        return launch_percentiles(dY, rows, (long)M, M, dq, nq, dOut, nullptr, dMean, stream);
     }
     return launch_percentiles(dX, rows, ldx, K, dq, nq, dOut, dExp, dMean, stream);
 }
@@ -175,34 +145,20 @@ int post_percentiles_device(const double *dX, int rows, int K, long ldx, const d
                             const double *q, int nq, double *out, const unsigned char *expcol, double *mean)
 {
     const int ncols = Phi ? M : K;
-    double *dPhi = nullptr, *dBias = nullptr, *dq = nullptr, *dOut = nullptr, *dMean = nullptr;
-    unsigned char *dExp = nullptr;
-    auto cleanup = [&]() { hipFree(dPhi); hipFree(dBias); hipFree(dq); hipFree(dOut); hipFree(dMean); hipFree(dExp); };
-#define PP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    if (Phi) {
-        PP_HIP(hipMalloc((void **)&dPhi, (size_t)M * K * sizeof(double)));
-        PP_HIP(hipMemcpy(dPhi, Phi, (size_t)M * K * sizeof(double), hipMemcpyHostToDevice));
-        if (bias) {
-            PP_HIP(hipMalloc((void **)&dBias, (size_t)M * sizeof(double)));
-            PP_HIP(hipMemcpy(dBias, bias, (size_t)M * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
+    DevBuf<double> dPhi, dBias, dq, dOut, dMean;
+    DevBuf<unsigned char> dExp;
+    if (Phi && upload(dPhi, Phi, (size_t)M * K)) return -10;
+    if (Phi && bias && upload(dBias, bias, (size_t)M)) return -10;
     std::vector<double> quant(nq);
     for (int t = 0; t < nq; ++t) quant[t] = q[t] / 100.0;           // np.true_divide(q, 100)
-    PP_HIP(hipMalloc((void **)&dq, (size_t)nq * sizeof(double)));
-    PP_HIP(hipMemcpy(dq, quant.data(), (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
-    PP_HIP(hipMalloc((void **)&dOut, (size_t)nq * ncols * sizeof(double)));
-    if (expcol && !Phi) {
-        PP_HIP(hipMalloc((void **)&dExp, (size_t)K));
-        PP_HIP(hipMemcpy(dExp, expcol, (size_t)K, hipMemcpyHostToDevice));
-    }
-    if (mean) PP_HIP(hipMalloc((void **)&dMean, (size_t)ncols * sizeof(double)));
+    if (upload(dq, quant.data(), (size_t)nq)) return -10;
+    BDRT_HIP(dOut.alloc((size_t)nq * ncols));
+    if (expcol && !Phi && upload(dExp, expcol, (size_t)K)) return -10;
+    if (mean) BDRT_HIP(dMean.alloc((size_t)ncols));
     const int rc = percentiles_dev(dX, rows, K, ldx, dPhi, M, dBias, dq, nq, dOut, dExp, dMean, nullptr);
-    if (rc) { cleanup(); return rc; }
-    PP_HIP(hipMemcpy(out, dOut, (size_t)nq * ncols * sizeof(double), hipMemcpyDeviceToHost));
-    if (mean) PP_HIP(hipMemcpy(mean, dMean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost));
-#undef PP_HIP
-    cleanup();
+    if (rc) return rc;
+    BDRT_HIP(hipMemcpy(out, dOut, (size_t)nq * ncols * sizeof(double), hipMemcpyDeviceToHost));
+    if (mean) BDRT_HIP(hipMemcpy(mean, dMean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -220,13 +176,9 @@ int bdrt_percentiles(const double *X, int rows, int K, long ldx, const double *P
         return -1;
     }
     bind_process_device();
-    double *dX = nullptr;
-    const size_t nb = ((size_t)(rows - 1) * ldx + K) * sizeof(double);
-    if (hipMalloc((void **)&dX, nb) != hipSuccess) { set_error("bdrt_percentiles: hipMalloc(%zu) failed", nb); return -10; }
-    if (hipMemcpy(dX, X, nb, hipMemcpyHostToDevice) != hipSuccess) { hipFree(dX); set_error("bdrt_percentiles: copy failed"); return -10; }
-    const int rc = post_percentiles_device(dX, rows, K, ldx, Phi, M, bias, q, nq, out);
-    hipFree(dX);
-    return rc;
+    DevBuf<double> dX;
+    if (upload_rows(dX, X, (size_t)rows, ldx, K)) return -10;
+    return post_percentiles_device(dX, rows, K, ldx, Phi, M, bias, q, nq, out);
 }
 
 int bdrt_summary(const double *X, int rows, int K, long ldx, const unsigned char *is_pos, const double *q, int nq,
@@ -234,13 +186,9 @@ int bdrt_summary(const double *X, int rows, int K, long ldx, const unsigned char
 {
     if (!X || rows < 1 || K < 1 || ldx < K || !q || nq < 1 || !pct) { set_error("bdrt_summary: bad arguments"); return -1; }
     bind_process_device();
-    double *dX = nullptr;
-    const size_t nb = ((size_t)(rows - 1) * ldx + K) * sizeof(double);
-    if (hipMalloc((void **)&dX, nb) != hipSuccess) { set_error("bdrt_summary: hipMalloc(%zu) failed", nb); return -10; }
-    if (hipMemcpy(dX, X, nb, hipMemcpyHostToDevice) != hipSuccess) { hipFree(dX); set_error("bdrt_summary: copy failed"); return -10; }
-    const int rc = post_percentiles_device(dX, rows, K, ldx, nullptr, 0, nullptr, q, nq, pct, is_pos, mean);
-    hipFree(dX);
-    return rc;
+    DevBuf<double> dX;
+    if (upload_rows(dX, X, (size_t)rows, ldx, K)) return -10;
+    return post_percentiles_device(dX, rows, K, ldx, nullptr, 0, nullptr, q, nq, pct, is_pos, mean);
 }
 
 }  // extern "C"

@@ -18,17 +18,18 @@
 //   6  wrk = 1[val <= q_lo], 1[val <= q_hi], val in turn -> ESS of each: ess_tail = the smaller of the first two, ess_mean;
 //      the last pass also gives sd
 // LDS per draw: 8 B val + 8 B wrk + 2 B index = 18 B, so RK_MAX_DRAWS = 8192 split draws take 144 KiB, plus 7.6 KiB of scratch.
-// No atomics; every sum has a fixed order, so a column gives the same bits alone or in any batch.  This file is compiled with
-// -ffp-contract=off: the products that accumulate are explicit fma() calls, everything else is rounded separately.
+// No atomics; every sum has a fixed order, so a column gives the same bits alone or in any batch (bdrt_stats.h: the reductions,
+// the sorting network, numpy's quantile, R-hat over rows and Geyer's sequence, shared with the other post-sampling statistics).
 #include <cmath>
 
 #include "bdrt_host.h"
+#include "bdrt_stats.h"
 
 namespace bdrt {
 
 constexpr int RK_NT = 512;                       // 8 waves
 constexpr int RK_NW = RK_NT / 64;
-constexpr int RK_LAGS = 64;                      // lags per block of the autocovariance loop (one per lane)
+constexpr int RK_LAGS = STATS_LAGS;               // lags per block of the autocovariance loop (one per lane)
 constexpr int RK_MAX_DRAWS = 8192;               // split draws per column (S)
 constexpr int RK_PER = RK_MAX_DRAWS / RK_NT;     // sorted positions per thread
 constexpr int RK_MAX_CHAINS = 64;
@@ -46,43 +47,16 @@ struct RankArgs {
     int zwhat;                                   // 0 z of the draws, 1 z of the folded draws, 2 the staged draws themselves
 };
 
-__device__ inline double rk_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// idx <- the permutation that sorts key ascending, ties by index.  Same-direction bitonic network of any length: a partner
-// past the end counts as +inf and never moves.
+// idx <- the permutation that sorts key ascending, ties by index
 __device__ inline void rk_sort(const double *key, unsigned short *idx, int S)
 {
     const int tid = threadIdx.x;
     for (int i = tid; i < S; i += RK_NT) idx[i] = (unsigned short)i;
-    int n2 = 1;
-    while (n2 < S) n2 <<= 1;
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int p = tid; p < (n2 >> 1); p += RK_NT) {
-                const int blk = p / j, off = p - blk * j;
-                int i, q;
-                if (j == (k >> 1)) {
-                    i = blk * k + off;
-                    q = blk * k + (k - 1 - off);
-                } else {
-                    i = blk * 2 * j + off;
-                    q = i + j;
-                }
-                if (q < S) {
-                    const unsigned short ia = idx[i], ib = idx[q];
-                    const double u = key[ia], v = key[ib];
-                    if (u > v || (u == v && ia > ib)) { idx[i] = ib; idx[q] = ia; }
-                }
-            }
-        }
-    }
-    __syncthreads();
+    bitonic_any<RK_NT>(S, [&](int i, int q) {
+        const unsigned short ia = idx[i], ib = idx[q];
+        const double u = key[ia], v = key[ib];
+        if (u > v || (u == v && ia > ib)) { idx[i] = ib; idx[q] = ia; }
+    });
 }
 
 // out[i] = z of the average rank of key[i] among all S keys; idx sorts key.  out may be key: every thread holds its z values
@@ -141,7 +115,7 @@ __device__ inline int rk_rows(double *wrk, int H, int n, double *cm, double *cs,
             rowdiff |= (v != r0);
             s += v;
         }
-        s = rk_wave_sum(s);
+        s = wave_sum(s);
         rowdiff = __any(rowdiff);
         differs |= rowdiff | (r0 != v00);
         if (lane == 0) { rs[h] = s; cm[h] = rowdiff ? s / (double)n : r0; }   // a row of equal values: that value, exactly
@@ -162,130 +136,28 @@ __device__ inline int rk_rows(double *wrk, int H, int n, double *cm, double *cs,
             gq = fma(e, e, gq);
             r[t] = d;
         }
-        q = rk_wave_sum(q);
+        q = wave_sum(q);
         if (lane == 0) cs[h] = q;
     }
-    gq = rk_wave_sum(gq);
-    if (lane == 0) part[w] = gq;
-    __syncthreads();
-    double g = part[0];
-#pragma unroll
-    for (int i = 1; i < RK_NW; ++i) g += part[i];
-    *gq_out = g;
+    *gq_out = block_sum<RK_NW>(gq, part);
     __syncthreads();
     return differs;
 }
 
-// R-hat over the H rows as chains, no further split (every thread computes the same value)
-__device__ inline double rk_rhat(int H, int n, const double *cm, const double *cs)
-{
-    if (n < 2) return NAN;
-    double hbar = 0.0, W = 0.0, B = 0.0;
-    for (int h = 0; h < H; ++h) hbar += cm[h];
-    hbar /= (double)H;
-    for (int h = 0; h < H; ++h) { const double d = cm[h] - hbar; B = fma(d, d, B); }
-    B = (double)n * (B / (double)(H - 1));
-    for (int h = 0; h < H; ++h) W += cs[h] / (double)(n - 1);
-    W /= (double)H;
-    return sqrt((B / W + (double)(n - 1)) / (double)n);
-}
-
-// Geyer's effective sample size (Stan 2.19, tests/diag_numpy.py `ess`) of H chains of n draws, capped at S log10 S: wrk is
-// centred by row, cm / cs are its row means and centred sums of squares (rk_rows).  The lag blocks, the summation order and
-// the pair walk are those of diag_kernel's pass 3.  The same value in every thread.
+// Geyer's effective sample size of the H rows of wrk as chains, capped at S log10 S; wrk is centred by row, cm / cs are its row
+// means and centred sums of squares (rk_rows).  NaN when no entry differs from the first.  The same value in every thread.
 __device__ inline double rk_ess(const double *wrk, int H, int n, int differs, const double *cm, const double *cs, double *part,
                                 double *rho, double *sc)
 {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (n < 4 || !differs) return NAN;
-    double mean_var = 0.0;
-    for (int h = 0; h < H; ++h) mean_var += (cs[h] / (double)n) * (double)n / (double)(n - 1);
-    mean_var /= (double)H;
-    double var_plus = mean_var * (double)(n - 1) / (double)n;
-    {
-        double mb = 0.0, vb = 0.0;
-        for (int h = 0; h < H; ++h) mb += cm[h];
-        mb /= (double)H;
-        for (int h = 0; h < H; ++h) { const double d = cm[h] - mb; vb = fma(d, d, vb); }
-        var_plus += vb / (double)(H - 1);
-    }
-    const int chunk = (n + RK_NW - 1) / RK_NW, tw0 = min(n, w * chunk), tw1 = min(n, tw0 + chunk);
-    double acc_pm = 0.0, prev_pm = 0.0;                               // thread 0: sum of monotone pair sums so far, last one
-    for (int k0 = 0;; k0 += RK_LAGS) {
-        const int k = k0 + lane;
-        double s = 0.0;
-        if (k < n) {
-            const int te = min(tw1, n - k);
-            for (int h = 0; h < H; ++h) {
-                const double *cc = wrk + (size_t)h * n;
-                for (int t = tw0; t < te; ++t) s = fma(cc[t], cc[t + k], s);
-            }
-        }
-        part[w * RK_LAGS + lane] = s;
-        __syncthreads();
-        if (tid < RK_LAGS) {
-            double T = part[tid];
-#pragma unroll
-            for (int i = 1; i < RK_NW; ++i) T += part[i * RK_LAGS + tid];
-            const double acov_mean = (T / (double)n) / (double)H;
-            rho[tid] = 1.0 - (mean_var - acov_mean) / var_plus;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double tau = NAN;
-            for (int l = 0; l < RK_LAGS && !(tau == tau); l += 2) {
-                const int jp = (k0 + l) >> 1;                         // pair jp = lags (2 jp, 2 jp + 1)
-                const double ev = jp == 0 ? 1.0 : rho[l], od = rho[l + 1];
-                const bool cont = (2 * jp + 1 < n - 4) && (ev + od > 0.0);
-                if (cont) {
-                    const double p = ev + od;
-                    const double pm = (jp == 0 || !(p > prev_pm)) ? p : prev_pm;
-                    acc_pm += pm;
-                    prev_pm = pm;
-                } else {
-                    const double e = (jp == 0 || ev + od >= 0.0) ? ev : 0.0;
-                    const double b = ev > 0.0 ? ev : 0.0;
-                    tau = -1.0 + 2.0 * (acc_pm + e) + b;
-                }
-            }
-            const bool done = (tau == tau) || k0 + RK_LAGS >= n;      // (the pair walk ends before lag n - 2)
-            sc[0] = done ? 1.0 : 0.0;
-            sc[1] = tau;
-        }
-        __syncthreads();
-        const bool done = sc[0] != 0.0;
-        const double tau = sc[1];
-        __syncthreads();
-        if (done) {
-            const double S = (double)(H * n);
-            const double e = S / tau;
-            return isfinite(e) ? fmin(e, S * log10(S)) : NAN;
-        }
-    }
+    if (!differs) return NAN;
+    const double tau = geyer_tau<RK_NW>([&](int h, int t) -> double { return wrk[(size_t)h * n + t]; }, H, n, cm, cs, part, rho, sc);
+    const double S = (double)(H * n);
+    const double e = S / tau;
+    return isfinite(e) ? fmin(e, S * log10(S)) : NAN;
 }
 
 __device__ inline double rk_nan_max(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 __device__ inline double rk_nan_min(double a, double b) { return (a != a || b != b) ? NAN : fmin(a, b); }
-
-// numpy's _lerp, as bdrt_post.hip's percentile kernel
-__device__ inline double rk_lerp(double a, double b, double t)
-{
-    const double d = b - a;
-    double r = a + d * t;
-    if (t >= 0.5) r = b - d * (1.0 - t);
-    return r;
-}
-
-// np.percentile(Y, 100 p) ('linear') from the sorted order; quant = (100 p) / 100
-__device__ inline double rk_quantile(const double *val, const unsigned short *idx, int S, double quant)
-{
-    const double virt = (double)(S - 1) * quant;
-    const double prev = floor(virt);
-    int lo = (int)prev, hi = lo + 1;
-    lo = lo < 0 ? 0 : (lo > S - 1 ? S - 1 : lo);
-    hi = hi < 0 ? 0 : (hi > S - 1 ? S - 1 : hi);
-    return rk_lerp(val[idx[lo]], val[idx[hi]], virt - prev);
-}
 
 __global__ __launch_bounds__(RK_NT) void rank_kernel(RankArgs a)
 {
@@ -336,8 +208,9 @@ __global__ __launch_bounds__(RK_NT) void rank_kernel(RankArgs a)
     // ---- 2, 3: sort, quantiles, z of the draws
     rk_sort(val, idx, S);
     if (tid == 0) {
-        sc[8] = rk_quantile(val, idx, S, a.q_lo);
-        sc[9] = rk_quantile(val, idx, S, a.q_hi);
+        const auto sorted = [&](int i) -> double { return val[idx[i]]; };
+        sc[8] = numpy_quantile(sorted, S, a.q_lo);                    // np.percentile(Y, 100 p): q_lo, q_hi = (100 p) / 100
+        sc[9] = numpy_quantile(sorted, S, a.q_hi);
         sc[10] = (S & 1) ? val[idx[S >> 1]] : (val[idx[(S >> 1) - 1]] + val[idx[S >> 1]]) / 2.0;
     }
     rk_rank_z(val, wrk, idx, S);
@@ -349,7 +222,7 @@ __global__ __launch_bounds__(RK_NT) void rank_kernel(RankArgs a)
     // ---- 4: R-hat and ESS of z
     double gq;
     int df = rk_rows(wrk, H, n, cm, cs, rs, part, &gq);
-    const double rhat_z = rk_rhat(H, n, cm, cs);
+    const double rhat_z = rhat_rows(H, n, cm, cs);
     const double ess_bulk = rk_ess(wrk, H, n, df, cm, cs, part, rho, sc);
     // ---- 5: folded draws
     __syncthreads();
@@ -362,7 +235,7 @@ __global__ __launch_bounds__(RK_NT) void rank_kernel(RankArgs a)
         return;
     }
     rk_rows(wrk, H, n, cm, cs, rs, part, &gq);
-    const double rhat_f = rk_rhat(H, n, cm, cs);
+    const double rhat_f = rhat_rows(H, n, cm, cs);
     // ---- 6: the two indicator series and the draws themselves
     __syncthreads();
     for (int i = tid; i < S; i += RK_NT) wrk[i] = val[i] <= q_lo ? 1.0 : 0.0;
@@ -413,14 +286,13 @@ static int rank_launch(RankArgs a, int G, hipStream_t stream)
     }));
     double *outs[5] = {a.rhat, a.bulk, a.tail, a.essm, a.sd};
     const double *X0 = a.X;
-    for (int g0 = 0; g0 < G; g0 += 65535) {
-        const int gn = std::min(G - g0, 65535);
+    const int rc = for_grid_y_chunks(G, [&](int g0, int gn) {
         const size_t o = (size_t)g0 * a.C;
         a.X = X0 + (size_t)g0 * a.M * a.unit_stride;
         if (outs[0]) { a.rhat = outs[0] + o; a.bulk = outs[1] + o; a.tail = outs[2] + o; a.essm = outs[3] + o; a.sd = outs[4] + o; }
         hipLaunchKernelGGL(rank_kernel, dim3(a.C, gn), dim3(RK_NT), lds, stream, a);
-        BDRT_HIP(hipGetLastError());
-    }
+    });
+    if (rc) return rc;
     BDRT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
@@ -431,34 +303,21 @@ int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride
                              double *ess_mean, double *sd, hipStream_t stream)
 {
     if (rank_check_shape("bdrt rank diagnostics", G, M, N, C, p_lo, p_hi)) return -1;
-    double *dOut = nullptr;
-    unsigned char *dExp = nullptr;
-    const size_t gc = (size_t)G * C, nb = gc * sizeof(double);
-    hipError_t e = hipMalloc((void **)&dOut, 5 * nb);
-    if (e == hipSuccess && is_pos) {
-        e = hipMalloc((void **)&dExp, (size_t)C);
-        if (e == hipSuccess) e = hipMemcpy(dExp, is_pos, (size_t)C, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        hipFree(dOut); hipFree(dExp);
-        set_error("bdrt rank diagnostics: %s", hipGetErrorString(e));
-        return -10;
-    }
+    const size_t gc = (size_t)G * C;
+    DevBuf<double> dOut;
+    DevBuf<unsigned char> dExp;
+    BDRT_HIP(dOut.alloc(5 * gc));
+    if (is_pos && upload(dExp, is_pos, (size_t)C)) return -10;
     RankArgs a;
     a.X = dX; a.unit_stride = unit_stride; a.row_stride = row_stride; a.expcol = dExp;
     a.M = M; a.N = N; a.C = C;
     a.q_lo = (100.0 * p_lo) / 100.0; a.q_hi = (100.0 * p_hi) / 100.0;
     a.rhat = dOut; a.bulk = dOut + gc; a.tail = dOut + 2 * gc; a.essm = dOut + 3 * gc; a.sd = dOut + 4 * gc;
     a.zout = nullptr; a.zwhat = 0;
-    int rc = rank_launch(a, G, stream);
-    double *outs[5] = {rhat, ess_bulk, ess_tail, ess_mean, sd};
-    for (int k = 0; k < 5 && rc == 0; ++k) {
-        if (!outs[k]) continue;
-        e = hipMemcpy(outs[k], dOut + k * gc, nb, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error("bdrt rank diagnostics: %s", hipGetErrorString(e)); rc = -10; }
-    }
-    hipFree(dOut); hipFree(dExp);
-    return rc;
+    const int rc = rank_launch(a, G, stream);
+    if (rc) return rc;
+    double *const outs[5] = {rhat, ess_bulk, ess_tail, ess_mean, sd};
+    return download_planes(dOut, gc, outs, 5);
 }
 
 }  // namespace bdrt
@@ -475,18 +334,10 @@ int bdrt_rank_diagnostics(const double *X, int G, int M, int N, int C, long ldx,
     if (!X || ldx < C) { set_error("bdrt_rank_diagnostics: bad arguments"); return -1; }
     if (rank_check_shape("bdrt_rank_diagnostics", G, M, N, C, p_lo, p_hi)) return -1;
     bind_process_device();
-    double *dX = nullptr;
-    const size_t nb = ((size_t)G * M * N - 1) * ldx * sizeof(double) + (size_t)C * sizeof(double);
-    if (hipMalloc((void **)&dX, nb) != hipSuccess) { set_error("bdrt_rank_diagnostics: hipMalloc(%zu) failed", nb); return -10; }
-    if (hipMemcpy(dX, X, nb, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(dX);
-        set_error("bdrt_rank_diagnostics: copy failed");
-        return -10;
-    }
-    const int rc = rank_diagnostics_to_host(dX, (long)N * ldx, ldx, is_pos, G, M, N, C, p_lo, p_hi, rhat, ess_bulk, ess_tail,
-                                            ess_mean, sd, nullptr);
-    hipFree(dX);
-    return rc;
+    DevBuf<double> dX;
+    if (upload_rows(dX, X, (size_t)G * M * N, ldx, C)) return -10;
+    return rank_diagnostics_to_host(dX, (long)N * ldx, ldx, is_pos, G, M, N, C, p_lo, p_hi, rhat, ess_bulk, ess_tail, ess_mean, sd,
+                                    nullptr);
 }
 
 int bdrt_debug_rank_z(const double *y, int M, int N, int is_pos, int what, double *z_out)
@@ -494,33 +345,22 @@ int bdrt_debug_rank_z(const double *y, int M, int N, int is_pos, int what, doubl
     if (!y || !z_out || what < 0 || what > 2) { set_error("bdrt_debug_rank_z: bad arguments"); return -1; }
     if (rank_check_shape("bdrt_debug_rank_z", 1, M, N, 1, 0.05, 0.95)) return -1;
     bind_process_device();
-    const size_t nin = (size_t)M * N * sizeof(double), nout = (size_t)2 * M * (N / 2) * sizeof(double);
-    double *dX = nullptr, *dZ = nullptr;
-    unsigned char *dExp = nullptr;
+    const size_t nout = (size_t)2 * M * (N / 2);
     const unsigned char flag = is_pos != 0;
-    hipError_t e = hipMalloc((void **)&dX, nin);
-    if (e == hipSuccess) e = hipMalloc((void **)&dZ, nout);
-    if (e == hipSuccess) e = hipMalloc((void **)&dExp, 1);
-    if (e == hipSuccess) e = hipMemcpy(dX, y, nin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dExp, &flag, 1, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(dX); hipFree(dZ); hipFree(dExp);
-        set_error("bdrt_debug_rank_z: %s", hipGetErrorString(e));
-        return -10;
-    }
+    DevBuf<double> dX, dZ;
+    DevBuf<unsigned char> dExp;
+    if (upload(dX, y, (size_t)M * N) || upload(dExp, &flag, 1)) return -10;
+    BDRT_HIP(dZ.alloc(nout));
     RankArgs a;
     a.X = dX; a.unit_stride = N; a.row_stride = 1; a.expcol = dExp;
     a.M = M; a.N = N; a.C = 1;
     a.q_lo = 0.05; a.q_hi = 0.95;
     a.rhat = a.bulk = a.tail = a.essm = a.sd = nullptr;
     a.zout = dZ; a.zwhat = what;
-    int rc = rank_launch(a, 1, nullptr);
-    if (rc == 0 && hipMemcpy(z_out, dZ, nout, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("bdrt_debug_rank_z: copy failed");
-        rc = -10;
-    }
-    hipFree(dX); hipFree(dZ); hipFree(dExp);
-    return rc;
+    const int rc = rank_launch(a, 1, nullptr);
+    if (rc) return rc;
+    BDRT_HIP(hipMemcpy(z_out, dZ, nout * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // extern "C"

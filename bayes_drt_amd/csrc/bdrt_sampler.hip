@@ -676,36 +676,48 @@ int bdrt_sampler_phase_profile(bdrt_sampler *s, int enable, long long *cycles32)
     return 0;
 }
 
+// Common front of the four reductions over a sampler's draws: units [unit_lo, unit_hi) must exist, hold draws and, with
+// chains_per_group > 0, split into groups of that many chains.  Binds the calling thread to the sampler's device, waits for the
+// sampler's stream and gives the first draw of unit_lo in *dX.  who: the caller's name and its word for the range, which open
+// the message ("bdrt_sampler_summary: bad unit" range).
+static int sampler_draws(const char *who, bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, const double **dX)
+{
+    Sampler &S = s->impl;
+    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || (chains_per_group && (unit_hi - unit_lo) % chains_per_group) ||
+        S.np.n_draws < 1) {
+        set_error("%s range", who);
+        return -1;
+    }
+    BDRT_HIP(hipSetDevice(S.prob->device));
+    BDRT_HIP(hipStreamSynchronize(S.stream));
+    *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
+    return 0;
+}
+
 int bdrt_sampler_percentiles(bdrt_sampler *s, int unit_lo, int unit_hi, int col0, int ncols, const double *Phi, int M,
                              const double *bias, const double *q, int nq, double *out)
 {
     if (!s || !q || nq < 1 || !out) { set_error("bdrt_sampler_percentiles: null argument"); return -1; }
     Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || col0 < 0 || ncols < 1 || col0 + ncols > S.D ||
-        (Phi && M < 1) || S.np.n_draws < 1) {
+    if (col0 < 0 || ncols < 1 || col0 + ncols > S.D || (Phi && M < 1)) {
         set_error("bdrt_sampler_percentiles: bad unit / column range");
         return -1;
     }
-    BDRT_HIP(hipStreamSynchronize(S.stream));
+    const double *dX;
+    if (int rc = sampler_draws("bdrt_sampler_percentiles: bad unit / column", s, unit_lo, unit_hi, 0, &dX)) return rc;
     const long rows = (long)(unit_hi - unit_lo) * S.np.n_draws;
     if (rows > (1L << 30)) { set_error("bdrt_sampler_percentiles: too many rows"); return -1; }
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D + col0;
-    return post_percentiles_device(dX, (int)rows, ncols, (long)S.D, Phi, M, bias, q, nq, out);
+    return post_percentiles_device(dX + col0, (int)rows, ncols, (long)S.D, Phi, M, bias, q, nq, out);
 }
 
 int bdrt_sampler_summary(bdrt_sampler *s, int unit_lo, int unit_hi, const double *q, int nq, double *mean, double *pct)
 {
     if (!s || !q || nq < 1 || !pct) { set_error("bdrt_sampler_summary: null argument"); return -1; }
     Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_summary: bad unit range");
-        return -1;
-    }
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
+    const double *dX;
+    if (int rc = sampler_draws("bdrt_sampler_summary: bad unit", s, unit_lo, unit_hi, 0, &dX)) return rc;
     const long rows = (long)(unit_hi - unit_lo) * S.np.n_draws;
     if (rows > (1L << 30)) { set_error("bdrt_sampler_summary: too many rows"); return -1; }
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
     return post_percentiles_device(dX, (int)rows, S.D, (long)S.D, nullptr, 0, nullptr, q, nq, pct, S.prob->is_pos.data(), mean);
 }
 
@@ -714,13 +726,8 @@ int bdrt_sampler_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
 {
     if (!s || chains_per_group < 1) { set_error("bdrt_sampler_diagnostics: bad arguments"); return -1; }
     Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || (unit_hi - unit_lo) % chains_per_group || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_diagnostics: bad unit range");
-        return -1;
-    }
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
+    const double *dX;
+    if (int rc = sampler_draws("bdrt_sampler_diagnostics: bad unit", s, unit_lo, unit_hi, chains_per_group, &dX)) return rc;
     return diagnostics_to_host(dX, (long)S.np.n_draws * S.D, (long)S.D, S.prob->is_pos.data(), (unit_hi - unit_lo) / chains_per_group,
                                chains_per_group, S.np.n_draws, S.D, mean, sd, n_eff, rhat, S.stream);
 }
@@ -730,13 +737,8 @@ int bdrt_sampler_rank_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int
 {
     if (!s || chains_per_group < 1) { set_error("bdrt_sampler_rank_diagnostics: bad arguments"); return -1; }
     Sampler &S = s->impl;
-    if (unit_lo < 0 || unit_hi > S.n_units || unit_lo >= unit_hi || (unit_hi - unit_lo) % chains_per_group || S.np.n_draws < 1) {
-        set_error("bdrt_sampler_rank_diagnostics: bad unit range");
-        return -1;
-    }
-    BDRT_HIP(hipSetDevice(S.prob->device));
-    BDRT_HIP(hipStreamSynchronize(S.stream));
-    const double *dX = S.args.draws + (size_t)unit_lo * S.np.n_draws * S.D;
+    const double *dX;
+    if (int rc = sampler_draws("bdrt_sampler_rank_diagnostics: bad unit", s, unit_lo, unit_hi, chains_per_group, &dX)) return rc;
     return rank_diagnostics_to_host(dX, (long)S.np.n_draws * S.D, (long)S.D, S.prob->is_pos.data(),
                                     (unit_hi - unit_lo) / chains_per_group, chains_per_group, S.np.n_draws, S.D, p_lo, p_hi, rhat,
                                     ess_bulk, ess_tail, ess_mean, sd, S.stream);

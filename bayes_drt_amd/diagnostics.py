@@ -193,21 +193,34 @@ def _derive_saved(fit, nm):
 
 
 # ---------------------------------------------------------------------------------------------------- device reductions
-def column_diagnostics(X, chains, is_pos=None):
-    """mean, sd, n_eff, Rhat [G x C] of X [G groups, chains * draws, C columns] (or [chains * draws, C]: G = 1) on the GPU."""
-    lib = _lib.require_gpu()
+def _host_draws(X, chains, is_pos, who):
+    """(X as contiguous float64 [G, rows, C], whether it came as [rows, C], chains, is_pos as uint8 [C] or None) for the entry
+    points that take host draws.  ValueError before the library is touched: the C side reads rows * C doubles and C flags."""
     X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
     one = X.ndim == 2
     if one:
         X = X[None]
-    G, rows, Cn = X.shape
-    if rows % chains:
-        raise ValueError('column_diagnostics: %d draws do not split into %d chains' % (rows, chains))
+    if X.ndim != 3:
+        raise ValueError('%s: X must be [G, chains * draws, C] or [chains * draws, C]' % who)
+    rows, Cn = X.shape[1:]
+    chains = int(chains)
+    if chains < 1 or rows % chains:
+        raise ValueError('%s: %d draws do not split into %d chains' % (who, rows, chains))
     mask = None
     if is_pos is not None:
         mask = np.ascontiguousarray(np.asarray(is_pos, dtype=np.uint8))
+        if mask.shape != (Cn,):
+            raise ValueError('%s: is_pos must have one flag per column' % who)
+    return X, one, chains, mask
+
+
+def column_diagnostics(X, chains, is_pos=None):
+    """mean, sd, n_eff, Rhat [G x C] of X [G groups, chains * draws, C columns] (or [chains * draws, C]: G = 1) on the GPU."""
+    X, one, chains, mask = _host_draws(X, chains, is_pos, 'column_diagnostics')
+    G, rows, Cn = X.shape
+    lib = _lib.require_gpu()
     out = [np.empty((G, Cn)) for _ in range(4)]
-    _lib.check(lib.bdrt_diagnostics(_lib.ptr(X), G, int(chains), rows // chains, Cn, Cn, _lib.ptr(mask),
+    _lib.check(lib.bdrt_diagnostics(_lib.ptr(X), G, chains, rows // chains, Cn, Cn, _lib.ptr(mask),
                                     *[_lib.ptr(o) for o in out]), 'bdrt_diagnostics')
     return tuple(o[0] for o in out) if one else tuple(out)
 
@@ -257,23 +270,10 @@ def rank_diagnostics(X, chains, is_pos=None, tail_probs=TAIL_PROBS):
     the split chains: an odd number of draws per chain drops the middle draw, of 'sd' too.  ValueError when the draws do not
     split into the chains, for tail probabilities outside 0 < p_lo < p_hi < 1, and when one column has more split draws than
     the kernel holds in LDS (bdrt_rank_max_draws(): 8192, i.e. 8 chains x 1000 or 4 x 2000)."""
-    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
-    one = X.ndim == 2
-    if one:
-        X = X[None]
-    if X.ndim != 3:
-        raise ValueError('rank_diagnostics: X must be [G, chains * draws, C] or [chains * draws, C]')
+    X, one, chains, mask = _host_draws(X, chains, is_pos, 'rank_diagnostics')
     G, rows, Cn = X.shape
-    chains = int(chains)
-    if chains < 1 or rows % chains:
-        raise ValueError('rank_diagnostics: %d draws do not split into %d chains' % (rows, chains))
     p_lo, p_hi = _tail_probs(tail_probs, 'rank_diagnostics')
     _rank_shape('rank_diagnostics', chains, rows // chains)
-    mask = None
-    if is_pos is not None:
-        mask = np.ascontiguousarray(np.asarray(is_pos, dtype=np.uint8))
-        if mask.shape != (Cn,):
-            raise ValueError('rank_diagnostics: is_pos must have one flag per column')
     lib = _lib.require_gpu()
     out = [np.empty((G, Cn)) for _ in range(5)]
     if G and Cn:

@@ -123,3 +123,11 @@ def test_declared_order_and_saved_family():
                          'sigma_out_raw', 'sigma_out_scale']
     assert dict((n, s) for n, s, _ in d)['Z_hat'] == 20
     assert dg._saved_family({'xs': 0, 'xp': 0}) == 'Series-Parallel_StanModel.pkl'
+
+
+def test_column_diagnostics_checks_its_arrays_before_the_library():
+    X = np.zeros((8, 3))
+    with pytest.raises(ValueError, match='is_pos must have one flag per column'):
+        dg.column_diagnostics(X, 2, is_pos=[1, 0])                     # the C side would read 3 flags
+    with pytest.raises(ValueError, match='X must be'):
+        dg.column_diagnostics(np.zeros(8), 2)
