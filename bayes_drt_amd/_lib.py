@@ -76,7 +76,7 @@ SYMBOLS = [
     'bdrt_percentiles', 'bdrt_sampler_percentiles', 'bdrt_sampler_summary', 'bdrt_summary', 'bdrt_sampler_draws_dev',
     'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
     'bdrt_rank_diagnostics', 'bdrt_sampler_rank_diagnostics', 'bdrt_rank_max_draws',
-    'bdrt_pointwise_loglik', 'bdrt_psis_loo', 'bdrt_psis_loo_max_draws',
+    'bdrt_pointwise_loglik', 'bdrt_psis_loo', 'bdrt_psis_loo_max_draws', 'bdrt_psis_predict', 'bdrt_psis_predict_max_draws',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
 ]
@@ -194,6 +194,9 @@ def load_library():
     lib.bdrt_psis_loo.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.bdrt_psis_loo_max_draws.argtypes = []
     lib.bdrt_psis_loo_max_draws.restype = C.c_int
+    lib.bdrt_psis_predict.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp] + [vp] * 8
+    lib.bdrt_psis_predict_max_draws.argtypes = []
+    lib.bdrt_psis_predict_max_draws.restype = C.c_int
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

@@ -20,21 +20,18 @@
 //        -> elpd_loo, pareto_k, n_tail
 // Every sum is a per-thread strided partial, a wave butterfly and the eight wave partials added in order; the compaction order
 // (the one thing atomics decide) is erased by the sort.  So a column gives the same bits alone or in any batch.  The reductions
-// and the sorting network are bdrt_stats.h's; every product and sum is rounded separately, as in the numpy statement.
+// and the sorting network are bdrt_stats.h's; the log-likelihood of a point, the key, the radix select, the Pareto fit and the
+// smoothed tail value are bdrt_psis.h's, shared with bdrt_loo_predict.hip.  Every product and sum is rounded separately, as in
+// the numpy statement.
 #include <cfloat>
 #include <cmath>
 
 #include "bdrt_host.h"
-#include "bdrt_stats.h"
+#include "bdrt_psis.h"
 
 namespace bdrt {
 
-constexpr int LO_NT = 512;                       // 8 waves
-constexpr int LO_NW = LO_NT / 64;
-constexpr int LO_MAX_S = 16384;                  // draws per column: 128 KiB column + 26 KiB tail + scratch <= 160 KiB
-constexpr int LO_MAX_M = 96;                     // b_j of the Pareto fit: 30 + sqrt(ceil(16384 / 5)) = 87
-constexpr int LO_TILE = 32;
-
+// LO_MAX_S draws per column: 128 KiB column + 26 KiB tail + scratch <= 160 KiB of LDS
 __global__ __launch_bounds__(256) void loglik_kernel(const double *__restrict__ Zhat, const double *__restrict__ sig,
                                                      const double *__restrict__ z, size_t rows, int S, int N2, int pair,
                                                      double c0, double *__restrict__ out)
@@ -49,10 +46,7 @@ __global__ __launch_bounds__(256) void loglik_kernel(const double *__restrict__ 
         double acc = 0.0;
         for (int h = 0; h <= pair; ++h) {
             const int c = j + h * No;
-            const double s = sig[r * N2 + c];
-            const double q = (z[g * N2 + c] - Zhat[r * N2 + c]) / s;
-            double v = (c0 - log(s)) - 0.5 * (q * q);
-            if (!(s > 0.0) || !isfinite(s)) v = NAN;
+            const double v = lo_normal_loglik(z[g * N2 + c], Zhat[r * N2 + c], sig[r * N2 + c], c0);
             acc = h ? acc + v : v;
         }
         out[e] = acc;
@@ -94,32 +88,10 @@ struct LooArgs {
     int *ntail;
 };
 
-// order-preserving key of a double (no NaN here): larger value <=> larger key
-__device__ inline unsigned long long lo_key(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ inline double lo_unkey(unsigned long long k)
-{
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
-__device__ inline double lo_gpinv(double p, double k, double sigma)
-{
-    if (!(sigma > 0.0)) return NAN;
-    double x;
-    if (fabs(k) < DBL_EPSILON) x = -log1p(-p);
-    else x = expm1(-k * log1p(-p)) / k;
-    return x * sigma;
-}
-
 __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int S = a.S;
     const size_t c = blockIdx.x;
     double *col = lds;                                                // [S]      ll, then x, then y | smoothed tail
@@ -173,61 +145,7 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
     __syncthreads();
     for (int s = tid; s < S; s += LO_NT) col[s] = mn - col[s];
     // ---- 3: radix select of the (M+1)-th largest
-    int rank = a.M[c] + 1;
-    unsigned long long prefix = 0;
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 56 - 8 * pass;
-        __syncthreads();
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        for (int base = 0; base < S; base += LO_NT) {
-            const int s = base + tid;
-            bool act = s < S;
-            const unsigned long long key = act ? lo_key(col[s]) : 0ull;
-            if (pass > 0) act = act && ((key >> (shift + 8)) == prefix);
-            const int bin = (int)((key >> shift) & 255ull);
-            const unsigned long long am = __ballot(act);
-            if (am) {
-                const int first = __ffsll((long long)am) - 1;
-                const int b0 = __shfl(bin, first, 64);
-                const unsigned long long same = __ballot(act && bin == b0);
-                if (act) {
-                    if (bin == b0) {
-                        if (lane == first) atomicAdd(&hist[b0], __popcll(same));
-                    } else {
-                        atomicAdd(&hist[bin], 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (w == 0) {
-            const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-            const int own = (h0 + h1) + (h2 + h3);
-            int suf = own;                                            // elements in the bins of lanes >= this one
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_down(suf, o, 64);
-                if (lane + o < 64) suf += t;
-            }
-            const int above = suf - own;
-            if (above < rank && rank <= suf) {                        // exactly one lane
-                int acc = above, sel = 4 * lane + 3, left = rank - acc;
-                if (rank > acc + h3) {
-                    acc += h3; sel = 4 * lane + 2; left = rank - acc;
-                    if (rank > acc + h2) {
-                        acc += h2; sel = 4 * lane + 1; left = rank - acc;
-                        if (rank > acc + h1) { acc += h1; sel = 4 * lane; left = rank - acc; }
-                    }
-                }
-                si[0] = sel; si[1] = left;
-            }
-        }
-        __syncthreads();
-        prefix = (prefix << 8) | (unsigned long long)si[0];
-        rank = si[1];
-    }
-    const double cutoff = fmax(lo_unkey(prefix), a.log_dbl_min);
+    const double cutoff = fmax(lo_radix_select(col, S, a.M[c] + 1, hist, si), a.log_dbl_min);
     const double ecut = exp(cutoff);
     // ---- 4: compact the tail, sum the body
     __syncthreads();
@@ -263,51 +181,7 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
     // ---- 6: generalised-Pareto fit to y = exp(tail) - exp(cutoff)
     double khat = INFINITY, sigma = NAN;
     double *y = col, *sm = col + a.cap;                               // 2 cap <= S for S >= 4; else n <= 4 and neither is used
-    if (n > 4) {
-        for (int r = tid; r < n; r += LO_NT) y[r] = exp(tail[r]) - ecut;
-        __syncthreads();
-        const int m = min(30 + (int)sqrt((double)n), LO_MAX_M);
-        const double dn = (double)n;
-        if (tid < m) {
-            double b = 1.0 - sqrt((double)m / ((double)(tid + 1) - 0.5));
-            b /= 3.0 * y[(int)(dn / 4.0 + 0.5) - 1];
-            b += 1.0 / y[n - 1];
-            bj[tid] = b;
-        }
-        __syncthreads();
-        for (int j = w; j < m; j += LO_NW) {
-            const double nb = -bj[j];
-            double s = 0.0;
-            for (int r = lane; r < n; r += 64) s += log1p(nb * y[r]);
-            s = wave_sum(s);
-            if (lane == 0) kj[j] = s / dn;
-        }
-        __syncthreads();
-        if (tid < m) Lj[tid] = dn * ((log(-bj[tid] / kj[tid]) - kj[tid]) - 1.0);
-        __syncthreads();
-        if (tid < m) {
-            double s = 0.0;
-            const double L = Lj[tid];
-            for (int i = 0; i < m; ++i) s += exp(Lj[i] - L);
-            wj[tid] = 1.0 / s;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double sw = 0.0, bp = 0.0;
-            for (int j = 0; j < m; ++j)
-                if (wj[j] >= 10.0 * DBL_EPSILON) sw += wj[j];
-            for (int j = 0; j < m; ++j)
-                if (wj[j] >= 10.0 * DBL_EPSILON) bp += bj[j] * (wj[j] / sw);
-            sc[0] = bp;
-        }
-        __syncthreads();
-        const double bp = sc[0];
-        double s = 0.0;
-        for (int r = tid; r < n; r += LO_NT) s += log1p(-bp * y[r]);
-        const double km = block_sum<LO_NW>(s, red) / dn;
-        sigma = -km / bp;
-        khat = (dn * km + 5.0) / (dn + 10.0);
-    }
+    if (n > 4) lo_pareto_fit(tail, y, n, ecut, bj, kj, Lj, wj, sc, red, khat, sigma);
     // ---- 7: smoothed tail, the tail sums, results
     const bool smooth = n > 4 && isfinite(khat);
     double mt = -INFINITY, ut = -INFINITY;
@@ -315,8 +189,7 @@ __global__ __launch_bounds__(LO_NT) void psis_kernel(LooArgs a)
         const double t = tail[r];
         double v = t;
         if (smooth) {
-            v = log(lo_gpinv(((double)r + 0.5) / (double)n, khat, sigma) + ecut);
-            if (v > 0.0) v = 0.0;
+            v = lo_smoothed(r, n, khat, sigma, ecut);
             sm[r] = v;
         }
         mt = fmax(mt, v);
@@ -355,16 +228,26 @@ static size_t loo_lds_bytes(int S, int cap)
 }
 
 // tail length M = ceil(min(S / 5, 3 sqrt(S / reff))), as the numpy statement computes it (host arithmetic)
-static int loo_tail_lengths(int S, size_t ncol, const double *reff, std::vector<int> &M)
+int loo_tail_lengths(const char *who, int S, size_t ncol, const double *reff, std::vector<int> &M)
 {
     M.resize(ncol);
     const int cap = (S + 4) / 5;
     for (size_t i = 0; i < ncol; ++i) {
         const double r = reff ? reff[i] : 1.0;
-        if (!(r > 0.0) || !std::isfinite(r)) { set_error("bdrt_psis_loo: reff[%zu] = %g is not a positive number", i, r); return -1; }
+        if (!(r > 0.0) || !std::isfinite(r)) { set_error("%s: reff[%zu] = %g is not a positive number", who, i, r); return -1; }
         const double v = std::ceil(std::min((double)S / 5.0, 3.0 * std::sqrt((double)S / r)));
         M[i] = std::max(1, std::min(cap, (int)v));
     }
+    return 0;
+}
+
+int loo_transpose_device(const char *who, const double *dIn, double *dT, int G, int S, int N)
+{
+    const int tilesS = (S + LO_TILE - 1) / LO_TILE, tilesN = (N + LO_TILE - 1) / LO_TILE;
+    const size_t tiles = (size_t)G * tilesS * tilesN;
+    if (tiles > 0x7fffffffull) { set_error("%s: too many tiles", who); return -2; }
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, dIn, dT, S, N, tilesS, tilesN);
+    BDRT_HIP(hipGetLastError());
     return 0;
 }
 
@@ -408,7 +291,7 @@ int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, dou
     const size_t ncol = (size_t)G * N;
     if (ncol > 0x7fffffffull) { set_error("bdrt_psis_loo: too many columns"); return -2; }
     std::vector<int> M;
-    if (loo_tail_lengths(S, ncol, reff, M)) return -1;
+    if (loo_tail_lengths("bdrt_psis_loo", S, ncol, reff, M)) return -1;
     bind_process_device();
     const int cap = (S + 4) / 5;
     const size_t lds = loo_lds_bytes(S, cap), nel = ncol * S;
@@ -418,12 +301,7 @@ int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, dou
     BDRT_HIP(dT.alloc(nel));
     BDRT_HIP(dOut.alloc(4 * ncol));
     BDRT_HIP(dNtail.alloc(ncol));
-    const int tilesS = (S + LO_TILE - 1) / LO_TILE, tilesN = (N + LO_TILE - 1) / LO_TILE;
-    const size_t tiles = (size_t)G * tilesS * tilesN;
-    if (tiles > 0x7fffffffull) { set_error("bdrt_psis_loo: too many tiles"); return -2; }
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const double *)dIn, (double *)dT, S, N,
-                       tilesS, tilesN);
-    BDRT_HIP(hipGetLastError());
+    if (const int rc = loo_transpose_device("bdrt_psis_loo", dIn, dT, G, S, N)) return rc;
     static LdsAttrCache cache;
     BDRT_HIP(cache.ensure(lds, [&]() {
         return hipFuncSetAttribute((const void *)psis_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

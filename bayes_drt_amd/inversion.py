@@ -8,6 +8,7 @@ with `from bayes_drt_amd.inversion import Inverter`.  What runs where:
   * `ridge_fit` Gram + QP       -> bdrt_gram (MFMA) + bdrt_qp_box_batch (interior point on the GPU, replaces cvxopt)
   * `ridge_fit_many`            -> bdrt_gram_batch (all spectra of a grid in one launch) + bdrt_ridge_ex (all fits in one batch)
   * `loo` / `loo_many`           -> bdrt_pointwise_loglik + bdrt_psis_loo (PSIS-LOO and WAIC of sampling fits, loo.py)
+  * `loo_predict` / `loo_predict_many` / `loo_outliers` -> bdrt_psis_predict (LOO predictive mean, sd, PIT and residuals)
   * scaling, weights, Stan data dict, prediction algebra: numpy on the host (not hot: microseconds)
 Out of scope (drift fits, MultiDist, fitY/SA, peak fitting, plotting, file loaders) raise
 NotImplementedError instead of silently doing something else.
@@ -1807,6 +1808,73 @@ class Inverter:
         for inv, r in zip(inverters, res):
             inv.loo_result = r
         return res
+
+    def _loo_predict_view(self, r, part, freq):
+        """LooPredictResult of the scaled data -> the report in the units of the impedance as supplied."""
+        from . import loo as _loo
+        nf = len(freq)
+        sc = float(self._Z_scale)
+        half = {'real': ('re',), 'imag': ('im',), 'both': ('re', 'im')}[part]
+        nan = np.full(nf, np.nan)
+
+        def parts(v):
+            """the [nf] real and imaginary halves of a per-scalar array (NaN for a half that was not asked for)"""
+            v = np.asarray(v)
+            return {'re': v[:nf] if 're' in half else nan, 'im': v[nf * (len(half) - 1):] if 'im' in half else nan}
+
+        out = _loo.LooPredictResult(frequencies=np.array(freq, dtype=float), pareto_k=r.pareto_k, n_tail=r.n_tail,
+                                    n_bad_k=r.n_bad_k, n_draws=r.n_draws, pit_ks=r.pit_ks, pit_ks_p=r.pit_ks_p)
+        for tag, src in (('loo', ''), ('post', '_post')):
+            m, s, p, e = parts(r['mean' + src]), parts(r['sd' + src]), parts(r['pit' + src]), parts(r['resid' + src])
+            out['Z_' + tag] = np.empty(nf, dtype=complex)                    # (a NaN half must not spread to the other)
+            out['Z_' + tag].real, out['Z_' + tag].imag = m['re'] * sc, m['im'] * sc
+            for h in ('re', 'im'):
+                out['sigma_%s_%s' % (tag, h)] = s[h] * sc
+                out['pit_%s%s' % ('' if tag == 'loo' else 'post_', h)] = p[h]
+                out['resid_%s%s' % ('' if tag == 'loo' else 'post_', h)] = e[h]
+        return out
+
+    def loo_predict(self, unit='frequency', part='both', reff='auto'):
+        """Leave-one-out predictive check of this instance's sampling fit (bayes_drt_amd.loo.loo_predict): for every frequency
+        the prediction of a fit that has not seen it -- `Z_loo` (complex), `sigma_loo_re/_im`, the LOO-PIT `pit_re/_im` (uniform
+        on (0, 1) when the error model is calibrated; `pit_ks`, `pit_ks_p`: its Kolmogorov-Smirnov distance from that and the
+        asymptotic p-value) and the residuals `resid_re/_im` = (Z - Z_loo) / sigma_loo -- beside the in-sample posterior
+        predictive (`Z_post`, `sigma_post_re/_im`, `pit_post_re/_im`, `resid_post_re/_im`), `pareto_k` and `n_tail` per unit and
+        `frequencies`.  Means and sds are in the units of the impedance as supplied.  unit, part and reff as in `loo`: with
+        part = 'real' / 'imag' only that half is filled (the other is NaN) and units are points.
+        Stores the result as `loo_predict_result` and returns it."""
+        from . import loo as _loo
+        fit, z, columns, freq = self._loo_job(part)
+        r = _loo.loo_predict(fit, z, unit=unit, reff=reff, columns=columns, frequencies=freq)
+        self.loo_predict_result = self._loo_predict_view(r, part, freq)
+        return self.loo_predict_result
+
+    @staticmethod
+    def loo_predict_many(inverters, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+        """`loo_predict()` of every Inverter of a list (what `fit_many` returns), launched as `loo_many` launches: returns the
+        results in input order, each bit for bit what the Inverter's own `loo_predict()` gives, and stores each as
+        `loo_predict_result`."""
+        from . import loo as _loo
+        jobs = [inv._loo_job(part) for inv in inverters]
+        if len({None if j[2] is None else (j[2].start, j[2].stop) for j in jobs}) > 1:
+            raise ValueError('loo_predict_many: the spectra do not have the same number of frequencies')
+        res = _loo.loo_predict_many([j[0] for j in jobs], [j[1] for j in jobs], unit=unit, reff=reff,
+                                    columns=jobs[0][2] if jobs else None, frequencies=[j[3] for j in jobs],
+                                    chunk_bytes=chunk_bytes or _loo.CHUNK_BYTES)
+        out = []
+        for inv, j, r in zip(inverters, jobs, res):
+            inv.loo_predict_result = inv._loo_predict_view(r, part, j[3])
+            out.append(inv.loo_predict_result)
+        return out
+
+    def loo_outliers(self, threshold=3.5):
+        """Indices of likely outliers by the LOO residuals: sqrt((resid_re^2 + resid_im^2) / 2) > threshold, the z-score of
+        `check_outliers` with the leave-one-out predictive in place of the in-sample fit (which the point itself has pulled
+        towards it).  Runs `loo_predict()` on the current fit (and so replaces `loo_predict_result`)."""
+        r = self.loo_predict()
+        with np.errstate(invalid='ignore'):
+            zs = np.sqrt((r['resid_re'] ** 2 + r['resid_im'] ** 2) / 2)
+            return np.argwhere(zs > threshold)
 
     # ================================================================== prediction (reference :2571-3311)
     def _get_prediction_matrices(self, frequencies, distributions):

@@ -1,4 +1,5 @@
-"""Model comparison of sampling fits: PSIS-LOO and WAIC (`loo`, `compare`), reduced on the GPU.
+"""Model comparison and predictive checks of sampling fits: PSIS-LOO and WAIC (`loo`, `compare`) and the leave-one-out
+predictive distribution of every observation (`loo_predict`: LOO-PIT and LOO residuals), reduced on the GPU.
 
 Stan users rank fits of one data set by the expected log pointwise predictive density, estimated by leave-one-out
 cross-validation of the posterior with Pareto-smoothed importance sampling (Vehtari, Gelman, Gabry 2017), and by WAIC.  Every
@@ -10,7 +11,15 @@ Units: an observation is one frequency (`unit='frequency'`: real plus imaginary 
 (`unit='point'`).  The Pareto shape k-hat of an observation says how much the posterior hinges on it: above 0.7 the
 importance-sampling estimate for that observation is unreliable (and the observation is influential).
 
-Out of scope: K-fold or exact refits and moment matching for high-k observations; LOO of MAP or ridge fits.
+Predictive checks (`loo_predict`): the LOO predictive distribution of a scalar observation is the mixture of the draws'
+normals under the smoothed weights of its unit, so its mean, its sd and its cdf at the datum (the LOO-PIT, uniform on (0, 1)
+when the error model is calibrated) are weighted sums over the draws (bdrt_loo_predict.hip, `bdrt_psis_predict`; definitions in
+tests/loo_predict_numpy.py).  The residual (z - mean) / sd judges a point by a fit that has not seen it, unlike the in-sample
+z-score of `Inverter.check_outliers`.  Among equal log ratios in the tail the draw with the smaller index gets the smaller
+smoothed weight.
+
+Out of scope: K-fold or exact refits and moment matching for high-k observations; LOO of MAP or ridge fits; predictive checks
+with replicated data, plots, and the sharded path of parallel.py.
 """
 import logging
 
@@ -35,9 +44,18 @@ class LooResult(dict):
             raise AttributeError(name) from None
 
 
+class LooPredictResult(LooResult):
+    """Result of `loo_predict`: a dict whose entries also read as attributes."""
+
+
 def max_draws():
     """Largest number of draws per observation the kernel holds."""
     return int(_lib.load_library().bdrt_psis_loo_max_draws())
+
+
+def predict_max_draws():
+    """Largest number of draws per unit `psis_predict` holds."""
+    return int(_lib.load_library().bdrt_psis_predict_max_draws())
 
 
 def _pair(unit):
@@ -95,6 +113,43 @@ def psis_loo(ll, reff=None):
     lpd, elpd, k, pw = [o[0] for o in outs] if one else outs
     return {'lpd': lpd, 'elpd_loo': elpd, 'p_loo': lpd - elpd, 'pareto_k': k, 'p_waic': pw, 'elpd_waic': lpd - pw,
             'n_tail': n_tail[0] if one else n_tail}
+
+
+PREDICT_FIELDS = ('mean', 'sd', 'pit', 'mean_post', 'sd_post', 'pit_post')
+
+
+def psis_predict(Zhat, sig, z, unit='frequency', reff=None):
+    """LOO predictive moments per scalar observation on the GPU: Zhat, sig [G, S, 2 Nf] and z [G, 2 Nf] (or [S, 2 Nf] and
+    [2 Nf]: G = 1).  A unit is one frequency (real plus imaginary part left out together) or one point; reff: None (1), a
+    number, or [G, units].  Returns a dict of mean, sd, pit (LOO) and mean_post, sd_post, pit_post (equal weights), each
+    [G, 2 Nf], and pareto_k (float), n_tail (int) [G, units] -- those two equal `psis_loo(pointwise_log_lik(...), reff)`'s."""
+    pair = _pair(unit)
+    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
+    one = Zhat.ndim == 2
+    if one:
+        Zhat, sig, z = Zhat[None], sig[None], z[None]
+    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
+        raise ValueError('psis_predict: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+    G, S, N2 = Zhat.shape
+    if pair and N2 % 2:
+        raise ValueError("psis_predict: unit='frequency' needs an even number of columns, not %d" % N2)
+    if S > predict_max_draws():
+        raise ValueError('psis_predict: %d draws per unit, the kernel holds at most %d' % (S, predict_max_draws()))
+    if S < 2:
+        raise ValueError('psis_predict: at least 2 draws are needed')
+    U = N2 // 2 if pair else N2
+    r = None
+    if reff is not None:
+        r = _lib.f64(np.broadcast_to(np.asarray(reff, dtype=float), (G, U)))
+        if not np.all(np.isfinite(r) & (r > 0)):
+            raise ValueError('psis_predict: reff must be positive and finite')
+    lib = _lib.require_gpu()
+    outs = [np.empty((G, N2)) for _ in PREDICT_FIELDS]
+    k, n_tail = np.empty((G, U)), np.empty((G, U), dtype=np.int32)
+    _lib.check(lib.bdrt_psis_predict(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, _lib.ptr(r),
+                                     *[_lib.ptr(o) for o in outs], _lib.ptr(k), _lib.ptr(n_tail)), 'bdrt_psis_predict')
+    res = dict(zip(PREDICT_FIELDS, outs), pareto_k=k, n_tail=n_tail)
+    return {key: v[0] for key, v in res.items()} if one else res
 
 
 def relative_efficiency(ll, chains):
@@ -203,6 +258,92 @@ def loo_many(fits, zs, chains=None, unit='frequency', reff='auto', log_scales=No
             for g, i in enumerate(sel):
                 out[i] = _result({k: v[g] for k, v in p.items()}, 2 if pair else 1, shape[0], log_scales[i], frequencies[i],
                                  'fit %d: ' % i)
+    return out
+
+
+def ks_uniform(p):
+    """Kolmogorov-Smirnov distance of the finite values of p from U(0, 1) and its asymptotic p-value, the Kolmogorov series
+    2 sum_{j >= 1} (-1)^(j - 1) exp(-2 j^2 n D^2).  (nan, nan) without a finite value."""
+    p = np.asarray(p, dtype=float).reshape(-1)
+    p = np.sort(p[np.isfinite(p)])
+    n = len(p)
+    if n == 0:
+        return float('nan'), float('nan')
+    i = np.arange(1, n + 1)
+    D = float(max(np.max(i / n - p), np.max(p - (i - 1) / n)))
+    t = n * D * D
+    j = np.arange(1, 101)                            # t > 0.04: the terms beyond j = 23 are below 1e-18; below it 1 - Q < 1e-10
+    q = 2.0 * float(np.sum((-1.0) ** (j - 1) * np.exp(-2.0 * j * j * t))) if t > 0.04 else 1.0
+    return D, min(max(q, 0.0), 1.0)
+
+
+def _predict_result(p, z, S, frequencies=None, prefix=''):
+    """Kernel outputs of one fit -> LooPredictResult; logs the k-hat and residual line."""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        resid, resid_post = (z - p['mean']) / p['sd'], (z - p['mean_post']) / p['sd_post']
+        bad = np.nonzero(p['pareto_k'] > K_THRESHOLD)[0]
+    ks, ks_p = ks_uniform(p['pit'])
+    res = LooPredictResult(resid=resid, resid_post=resid_post, n_bad_k=int(len(bad)), n_draws=int(S), pit_ks=ks, pit_ks_p=ks_p,
+                           **{k: p[k] for k in PREDICT_FIELDS + ('pareto_k', 'n_tail')})
+    fin = np.abs(resid[np.isfinite(resid)])
+    worst = int(np.nanargmax(np.abs(resid))) if len(fin) else -1
+    where = ''
+    if worst >= 0 and frequencies is not None and len(frequencies):
+        where = ' (f = %.4g Hz)' % float(np.asarray(frequencies, dtype=float)[worst % len(frequencies)])
+    logger.log(logging.WARNING if len(bad) else logging.INFO,
+               '%sLOO predictive check: %d of %d units have Pareto k > %.1f; largest |LOO residual| %.3g at observation %d%s; '
+               'LOO-PIT KS distance %.3g (p = %.3g)', prefix, len(bad), len(p['pareto_k']), K_THRESHOLD,
+               float(fin.max()) if len(fin) else float('nan'), worst, where, ks, ks_p)
+    return res
+
+
+def _predict_reff(reff, Zh, sg, zz, pair, chains):
+    if isinstance(reff, str):
+        if reff != 'auto':
+            raise ValueError("reff must be 'auto', None, a number or an array")
+        return relative_efficiency(pointwise_log_lik(Zh, sg, zz, 'frequency' if pair else 'point'), chains)
+    return reff
+
+
+def loo_predict(fit, z, chains=None, unit='frequency', reff='auto', columns=None, frequencies=None):
+    """LOO predictive check of a sampling fit (`StanFit` or `SavedFit`) against the data z [2 Nf] it was fitted to, on the
+    fit's scale; arguments as `loo`.  Returns a `LooPredictResult`: per scalar observation mean, sd and pit of its
+    leave-one-out predictive distribution, resid = (z - mean) / sd, and mean_post, sd_post, pit_post, resid_post of the
+    in-sample posterior predictive; per unit pareto_k and n_tail; n_bad_k (units with k > 0.7, whose LOO figures are
+    unreliable), n_draws, and pit_ks, pit_ks_p: the Kolmogorov-Smirnov distance of the finite LOO-PIT values from U(0, 1) and
+    its asymptotic p-value."""
+    pair = _pair(unit) if columns is None else 0
+    Zhat, sig, z = _fit_arrays(fit, z, columns)
+    chains = int(chains if chains is not None else getattr(fit, 'chains', 1))
+    p = psis_predict(Zhat, sig, z, 'frequency' if pair else 'point', _predict_reff(reff, Zhat, sig, z, pair, chains))
+    return _predict_result(p, z, Zhat.shape[0], frequencies)
+
+
+def loo_predict_many(fits, zs, chains=None, unit='frequency', reff='auto', columns=None, frequencies=None,
+                     chunk_bytes=CHUNK_BYTES):
+    """`loo_predict` of many fits, grouped and chunked as `loo_many`: results in input order, each equal to the single-fit
+    `loo_predict` bit for bit."""
+    n = len(fits)
+    frequencies = [None] * n if frequencies is None else list(frequencies)
+    pair = _pair(unit) if columns is None else 0
+    arrays = [_fit_arrays(f, z, columns) for f, z in zip(fits, zs)]
+    ch = [int(chains if chains is not None else getattr(f, 'chains', 1)) for f in fits]
+    groups = {}
+    for i, a in enumerate(arrays):
+        groups.setdefault((a[0].shape, ch[i]), []).append(i)
+    out = [None] * n
+    for (shape, m), idx in groups.items():
+        per_fit = 3 * shape[0] * shape[1] * 8
+        step = max(1, int(chunk_bytes // per_fit))
+        for k0 in range(0, len(idx), step):
+            sel = idx[k0:k0 + step]
+            Zh, sg, zz = [np.stack([arrays[i][j] for i in sel]) for j in range(3)]
+            r = _predict_reff(reff, Zh, sg, zz, pair, m)
+            if r is not None and np.ndim(r) == 1:
+                r = np.broadcast_to(r, (shape[1] // 2 if pair else shape[1],))[None].repeat(len(sel), 0)
+            p = psis_predict(Zh, sg, zz, 'frequency' if pair else 'point', r)
+            for g, i in enumerate(sel):
+                out[i] = _predict_result({k: v[g] for k, v in p.items()}, zz[g], shape[0], frequencies[i], 'fit %d: ' % i)
     return out
 
 

@@ -367,6 +367,19 @@ int bdrt_pointwise_loglik(const double *Zhat, const double *sig, const double *z
 int bdrt_psis_loo(const double *ll, int G, int S, int N, const double *reff, double *lpd, double *elpd_loo, double *pareto_k,
                   double *p_waic, int *n_tail);
 int bdrt_psis_loo_max_draws(void);
+/* PSIS-LOO predictive checks; definitions: tests/loo_predict_numpy.py.  A unit is one scalar observation (pair = 0, U = N2
+ * units per fit) or the real and the imaginary part of one frequency left out together (pair = 1, U = N2 / 2: scalars i and
+ * i + N2 / 2).  The unit's log-likelihoods, Pareto-smoothed weights, pareto_k and n_tail are those of bdrt_pointwise_loglik +
+ * bdrt_psis_loo to the bit (reff [G][U] or NULL).  Per scalar, outputs [G][N2]: mean and sd of the leave-one-out predictive
+ * distribution (the weighted mixture of the draws' normals) and pit, its cdf at the datum; mean_post, sd_post, pit_post: the
+ * same with equal weights (the in-sample posterior predictive).  Among equal log ratios in the tail the draw with the smaller
+ * index gets the smaller smoothed weight.  A unit with a non-finite log-likelihood gives NaN in all of its outputs (n_tail 0);
+ * one whose log-likelihoods are all equal keeps equal weights (pareto_k inf, n_tail 0).  Zhat, sig, z as above on the host.
+ * 2 <= S <= bdrt_psis_predict_max_draws() (-2 above).  Bit-reproducible, and a unit's results do not depend on the launch. */
+int bdrt_psis_predict(const double *Zhat, const double *sig, const double *z, int G, int S, int N2, int pair, const double *reff,
+                      double *mean, double *sd, double *pit, double *mean_post, double *sd_post, double *pit_post,
+                      double *pareto_k, int *n_tail);
+int bdrt_psis_predict_max_draws(void);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
