@@ -66,7 +66,13 @@ struct DevBuf {
     DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
     DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
     ~DevBuf() { reset(); }
-    hipError_t alloc(size_t n) { reset(); return hipMalloc((void **)&p, n * sizeof(T)); }
+    hipError_t alloc(size_t n)      // (a failed allocation leaves the owner empty)
+    {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
     void reset() { if (p) hipFree(p); p = nullptr; }
     T *release() { T *q = p; p = nullptr; return q; }
     operator T *() const { return p; }
@@ -79,6 +85,28 @@ int upload(DevBuf<T> &d, const T *h, size_t n)
 {
     BDRT_HIP(d.alloc(n));
     BDRT_HIP(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// h <- the n elements at d
+template <class T>
+int download(T *h, const T *d, size_t n)
+{
+    BDRT_HIP(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same two copies enqueued on a stream, between buffers that exist: the caller synchronises
+template <class T>
+int upload(T *d, const T *h, size_t n, hipStream_t stream)
+{
+    BDRT_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+template <class T>
+int download(T *h, const T *d, size_t n, hipStream_t stream)
+{
+    BDRT_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, stream));
     return 0;
 }
 
@@ -107,23 +135,46 @@ int for_grid_y_chunks(int G, F launch)
     return 0;
 }
 
+// owners of a stream / an event that live as long as the object that holds them (neither copied nor moved)
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+// Every device allocation of a problem is a member that frees itself.  MEMBER ORDER is the order of release: members are
+// destroyed last to first, so the stream and the event stand before every buffer -- the buffers are freed first (hipFree waits
+// for the device), then the event, then the stream.
 struct Problem {
+    Stream stream;
+    // problems beyond the LDS budget (bdrt_big.h): the event the last launch on the per-point workspace recorded (see d_bigws)
+    Event bigws_done;
     DevProblem dev;                 // device view (pointers are device pointers), host copy
-    DevProblem *d_dev = nullptr;    // the same struct in HBM: kernels take it by pointer (uniform scalar loads)
+    DevBuf<DevProblem> d_dev;       // the same struct in HBM: kernels take it by pointer (uniform scalar loads)
     int sync_dev();                 // upload `dev` to d_dev
-    std::vector<void *> allocs;     // owned device allocations
+    std::vector<DevBuf<char>> tables;   // the constant tables `dev` points to (matrices in fragment order, generators, ...)
     std::vector<unsigned char> is_pos;
-    hipStream_t stream = nullptr;
     size_t lds_bytes = 0;
     int device = 0;
-    double *d_Z = nullptr;
+    DevBuf<double> d_Z;
     size_t z_capacity = 0;          // doubles
     // host copies of the layout
     int o_x[MAXB], o_ups[MAXB], o_d[MAXB];
     // scratch buffers for host-pointer entry points (grown on demand)
-    double *d_theta = nullptr, *d_grad = nullptr, *d_lp = nullptr;
-    int *d_spec = nullptr;
-    size_t scratch_rows = 0;
+    DevBuf<double> d_theta, d_grad, d_lp;
+    DevBuf<int> d_spec;
+    size_t scratch_rows = 0;        // (0 after a failed growth)
     int ensure_scratch(size_t rows);
     // launch_logp_grad_few: which one-workgroup-per-point evaluator the problem takes (-1 not looked at yet, 0 none, 1 the
     // headline family's, 2 the general one), decided once -- the call is launch-latency-bound, host microseconds count
@@ -131,9 +182,8 @@ struct Problem {
     // problems beyond the LDS budget (bdrt_big.h): per-point workspace of the evaluator, grown on demand
     // (ONE buffer per problem, indexed by workgroup: launches on different streams take turns -- each waits for the event the
     // one before it recorded --, and the bookkeeping is under a mutex)
-    double *d_bigws = nullptr;
-    size_t bigws_doubles = 0;
-    hipEvent_t bigws_done = nullptr;
+    DevBuf<double> d_bigws;
+    size_t bigws_doubles = 0;       // (0 after a failed growth)
     std::mutex bigws_mu;
     int ensure_bigws(size_t doubles);
 };

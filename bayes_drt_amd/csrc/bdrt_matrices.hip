@@ -205,11 +205,9 @@ int bdrt_build_A_basis(const double *freq, int nf, const double *tau, int k, dou
     }
     bind_process_device();
     DevBuf<double> dF, dT, dV, dO;
-    BDRT_HIP(dF.alloc(nf)); BDRT_HIP(dT.alloc(k));
     const int nent = toeplitz ? nf + k : nf * k;
+    if (upload(dF, freq, (size_t)nf) || upload(dT, tau, (size_t)k)) return -10;
     BDRT_HIP(dV.alloc((size_t)nent)); BDRT_HIP(dO.alloc((size_t)nf * k));
-    BDRT_HIP(hipMemcpy(dF.p, freq, nf * sizeof(double), hipMemcpyHostToDevice));
-    BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
     const int wpb = 4;   // waves per block
     hipLaunchKernelGGL(build_A_entries, dim3((nent + wpb - 1) / wpb), dim3(64 * wpb), 0, 0, dF.p, nf,
                        dT.p, k, eps, kernel_id, part, dist_series, use_ct, k_ct, toeplitz, nent, basis_id,
@@ -217,8 +215,7 @@ int bdrt_build_A_basis(const double *freq, int nf, const double *tau, int k, dou
     BDRT_HIP(hipGetLastError());
     if (toeplitz) {
         double c0, r0;
-        BDRT_HIP(hipMemcpy(&c0, dV.p, sizeof(double), hipMemcpyDeviceToHost));
-        BDRT_HIP(hipMemcpy(&r0, dV.p + nf, sizeof(double), hipMemcpyDeviceToHost));
+        if (download(&c0, dV.p, 1) || download(&r0, dV.p + nf, 1)) return -10;
         if (!(c0 == r0)) {                       // matrices.py:239-241
             set_error("First entries of first row and column are not equal (%.17g vs %.17g)", r0, c0);
             return -2;
@@ -227,8 +224,7 @@ int bdrt_build_A_basis(const double *freq, int nf, const double *tau, int k, dou
                            dO.p);
         BDRT_HIP(hipGetLastError());
     }
-    BDRT_HIP(hipMemcpy(out, dO.p, (size_t)nf * k * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return download(out, dO.p, (size_t)nf * k);
 }
 
 int bdrt_build_L(const double *tau, int k, double eps, const double *coef4, double *out)
@@ -250,17 +246,12 @@ int bdrt_build_L_rect(const double *freq, int nf, const double *tau, int k, doub
     }
     bind_process_device();
     DevBuf<double> dF, dT, dO;
-    BDRT_HIP(dT.alloc(k)); BDRT_HIP(dO.alloc((size_t)nf * k));
-    if (freq) {
-        BDRT_HIP(dF.alloc(nf));
-        BDRT_HIP(hipMemcpy(dF.p, freq, nf * sizeof(double), hipMemcpyHostToDevice));
-    }
-    BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(build_L_kernel, dim3((nf * k + 255) / 256), dim3(256), 0, 0, freq ? dF.p : (const double *)nullptr,
+    if (upload(dT, tau, (size_t)k) || (freq && upload(dF, freq, (size_t)nf))) return -10;
+    BDRT_HIP(dO.alloc((size_t)nf * k));
+    hipLaunchKernelGGL(build_L_kernel, dim3((nf * k + 255) / 256), dim3(256), 0, 0, (const double *)dF.p,
                        nf, dT.p, k, eps, coef4[0], coef4[1], coef4[2], coef4[3], basis_id, dO.p);
     BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipMemcpy(out, dO.p, (size_t)nf * k * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return download(out, dO.p, (size_t)nf * k);
 }
 
 int bdrt_build_M(const double *tau, int k, double eps, const double *coef3, int toeplitz, double *out)
@@ -268,13 +259,12 @@ int bdrt_build_M(const double *tau, int k, double eps, const double *coef3, int 
     if (!tau || !coef3 || !out || k <= 0) { set_error("bdrt_build_M: bad arguments"); return -1; }
     bind_process_device();
     DevBuf<double> dT, dO;
-    BDRT_HIP(dT.alloc(k)); BDRT_HIP(dO.alloc((size_t)k * k));
-    BDRT_HIP(hipMemcpy(dT.p, tau, k * sizeof(double), hipMemcpyHostToDevice));
+    if (upload(dT, tau, (size_t)k)) return -10;
+    BDRT_HIP(dO.alloc((size_t)k * k));
     hipLaunchKernelGGL(build_M_kernel, dim3((k * k + 255) / 256), dim3(256), 0, 0, dT.p, k, eps, coef3[0],
                        coef3[1], coef3[2], toeplitz, dO.p);
     BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipMemcpy(out, dO.p, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return download(out, dO.p, (size_t)k * k);
 }
 
 }  // extern "C"

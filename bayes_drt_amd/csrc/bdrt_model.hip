@@ -44,17 +44,17 @@ static std::vector<double> pack_fragments(int tiles, int pairs, F elem)
 template <class T>
 static int upload(Problem &P, const std::vector<T> &h, const T **dptr)
 {
-    void *d = nullptr;
-    BDRT_HIP(hipMalloc(&d, h.size() * sizeof(T) + 16));
+    DevBuf<char> d;
+    BDRT_HIP(d.alloc(h.size() * sizeof(T) + 16));          // (16 bytes of slack: readers may run past the end by design)
     BDRT_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    P.allocs.push_back(d);
-    *dptr = (const T *)d;
+    *dptr = (const T *)d.p;
+    P.tables.push_back(std::move(d));
     return 0;
 }
 
 int Problem::sync_dev()
 {
-    if (!d_dev) BDRT_HIP(hipMalloc((void **)&d_dev, sizeof(DevProblem)));
+    if (!d_dev) BDRT_HIP(d_dev.alloc(1));
     BDRT_HIP(hipMemcpy(d_dev, &dev, sizeof(DevProblem), hipMemcpyHostToDevice));
     return 0;
 }
@@ -62,12 +62,12 @@ int Problem::sync_dev()
 int Problem::ensure_scratch(size_t rows)
 {
     if (rows <= scratch_rows) return 0;
-    size_t n = rows < 64 ? 64 : rows;
-    if (d_theta) { hipFree(d_theta); hipFree(d_grad); hipFree(d_lp); hipFree(d_spec); }
-    BDRT_HIP(hipMalloc((void **)&d_theta, n * dev.D * sizeof(double)));
-    BDRT_HIP(hipMalloc((void **)&d_grad, n * dev.D * sizeof(double)));
-    BDRT_HIP(hipMalloc((void **)&d_lp, n * sizeof(double)));
-    BDRT_HIP(hipMalloc((void **)&d_spec, n * sizeof(int)));
+    const size_t n = rows < 64 ? 64 : rows;
+    scratch_rows = 0;
+    BDRT_HIP(d_theta.alloc(n * dev.D));
+    BDRT_HIP(d_grad.alloc(n * dev.D));
+    BDRT_HIP(d_lp.alloc(n));
+    BDRT_HIP(d_spec.alloc(n));
     scratch_rows = n;
     return 0;
 }
@@ -89,9 +89,9 @@ __global__ __launch_bounds__(BIG_NT) void big_eval_kernel(const DevProblem *__re
 int Problem::ensure_bigws(size_t doubles)
 {
     if (doubles <= bigws_doubles) return 0;
-    // (growing: hipFree waits for the device, so no launch that was handed the old buffer is still running)
-    if (d_bigws) { hipFree(d_bigws); d_bigws = nullptr; bigws_doubles = 0; }
-    BDRT_HIP(hipMalloc((void **)&d_bigws, doubles * sizeof(double)));
+    // (growing: freeing the old buffer waits for the device, so no launch that was handed it is still running)
+    bigws_doubles = 0;
+    BDRT_HIP(d_bigws.alloc(doubles));
     bigws_doubles = doubles;
     return 0;
 }
@@ -353,7 +353,7 @@ static int build_problem(Problem &P, const bdrt_dat *dat)
     for (int n = 0; n < nf; ++n) w[n] = 2.0 * M_PI * dat->freq[n];
     int rc;
     if ((rc = upload(P, w, &D.w))) return rc;
-    BDRT_HIP(hipStreamCreateWithFlags(&P.stream, hipStreamNonBlocking));
+    BDRT_HIP(hipStreamCreateWithFlags(&P.stream.s, hipStreamNonBlocking));
     D.n_spectra = 0;
     return 0;
 }
@@ -364,10 +364,9 @@ static int set_Z(Problem &P, const double *Z, int n_spectra)
     // the sampler addresses a chain's spectrum by a 32-bit byte offset and reads up to SPEC_PAD doubles beyond a row's end
     if ((need + SPEC_PAD) * sizeof(double) >= ((size_t)1 << 31)) { set_error("spectra of one problem must stay below 2 GiB (%d given)", n_spectra); return -1; }
     if (need > P.z_capacity) {
-        if (P.d_Z) hipFree(P.d_Z);
-        P.d_Z = nullptr; P.z_capacity = 0;
-        BDRT_HIP(hipMalloc((void **)&P.d_Z, (need + SPEC_PAD) * sizeof(double)));
-        BDRT_HIP(hipMemset(P.d_Z + need, 0, SPEC_PAD * sizeof(double)));
+        P.z_capacity = 0;
+        BDRT_HIP(P.d_Z.alloc(need + SPEC_PAD));
+        BDRT_HIP(hipMemset(P.d_Z.p + need, 0, SPEC_PAD * sizeof(double)));
         P.z_capacity = need;
     }
     BDRT_HIP(hipMemcpy(P.d_Z, Z, need * sizeof(double), hipMemcpyHostToDevice));
@@ -443,10 +442,10 @@ int launch_logp_grad(Problem *p, const double *d_theta, const int *d_spec, int B
         const int grid = std::min(B, 1024);
         std::lock_guard<std::mutex> lock(p->bigws_mu);
         // the workspace is the problem's, not the stream's: this launch starts when the previous one (whatever its stream) is done
-        if (!p->bigws_done) BDRT_HIP(hipEventCreateWithFlags(&p->bigws_done, hipEventDisableTiming));
+        if (!p->bigws_done) BDRT_HIP(hipEventCreateWithFlags(&p->bigws_done.e, hipEventDisableTiming));
         else BDRT_HIP(hipStreamWaitEvent(stream, p->bigws_done, 0));
         if (int rc = p->ensure_bigws((size_t)grid * big_ws_doubles(p->dev))) return rc;
-        hipLaunchKernelGGL(big_eval_kernel, dim3(grid), dim3(BIG_NT), 0, stream, (const DevProblem *)p->d_dev, p->d_bigws, d_theta, d_spec, B,
+        hipLaunchKernelGGL(big_eval_kernel, dim3(grid), dim3(BIG_NT), 0, stream, (const DevProblem *)p->d_dev, p->d_bigws.p, d_theta, d_spec, B,
                            jacobian, d_lp, d_grad, d_params, d_Zhat, d_sig);
         BDRT_HIP(hipGetLastError());
         BDRT_HIP(hipEventRecord(p->bigws_done, stream));
@@ -563,19 +562,8 @@ bdrt_problem *bdrt_problem_create(const bdrt_dat *dat)
     return p;
 }
 
-void bdrt_problem_destroy(bdrt_problem *p)
-{
-    if (!p) return;
-    Problem &P = p->impl;
-    for (void *d : P.allocs) hipFree(d);
-    if (P.d_Z) hipFree(P.d_Z);
-    if (P.d_dev) hipFree(P.d_dev);
-    if (P.d_theta) { hipFree(P.d_theta); hipFree(P.d_grad); hipFree(P.d_lp); hipFree(P.d_spec); }
-    if (P.d_bigws) hipFree(P.d_bigws);
-    if (P.bigws_done) hipEventDestroy(P.bigws_done);
-    if (P.stream) hipStreamDestroy(P.stream);
-    delete p;
-}
+// (buffers, then the event, then the stream: the member order of Problem, bdrt_host.h)
+void bdrt_problem_destroy(bdrt_problem *p) { delete p; }
 
 int bdrt_num_params(const bdrt_problem *p) { return p ? p->impl.dev.D : -1; }
 int bdrt_problem_evaluator(const bdrt_problem *p)
@@ -621,28 +609,24 @@ int bdrt_debug_sum_by_lane(const double *in, double *out)
 {
     if (!in || !out) { set_error("bdrt_debug_sum_by_lane: bad arguments"); return -1; }
     bind_process_device();
-    double *di = nullptr, *dout = nullptr;
-    BDRT_HIP(hipMalloc((void **)&di, 512 * sizeof(double)));
-    BDRT_HIP(hipMalloc((void **)&dout, 128 * sizeof(double)));
+    DevBuf<double> di, dout;
+    BDRT_HIP(di.alloc(512));
+    BDRT_HIP(dout.alloc(128));
     BDRT_HIP(hipMemcpy(di, in, 512 * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sum_by_lane_kernel, dim3(1), dim3(64), 0, 0, di, dout);
-    BDRT_HIP(hipMemcpy(out, dout, 128 * sizeof(double), hipMemcpyDeviceToHost));
-    hipFree(di); hipFree(dout);
-    return 0;
+    hipLaunchKernelGGL(sum_by_lane_kernel, dim3(1), dim3(64), 0, 0, di.p, dout.p);
+    return download(out, dout.p, 128);
 }
 
 int bdrt_debug_lean_math(const double *x, int n, double *out)
 {
     if (!x || !out || n < 1) { set_error("bdrt_debug_lean_math: bad arguments"); return -1; }
     bind_process_device();
-    double *dx = nullptr, *dout = nullptr;
-    BDRT_HIP(hipMalloc((void **)&dx, (size_t)n * sizeof(double)));
-    BDRT_HIP(hipMalloc((void **)&dout, (size_t)3 * n * sizeof(double)));
+    DevBuf<double> dx, dout;
+    BDRT_HIP(dx.alloc((size_t)n));
+    BDRT_HIP(dout.alloc((size_t)3 * n));
     BDRT_HIP(hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lean_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, n, dout);
-    BDRT_HIP(hipMemcpy(out, dout, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(dout);
-    return 0;
+    hipLaunchKernelGGL(lean_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx.p, n, dout.p);
+    return download(out, dout.p, (size_t)3 * n);
 }
 
 int bdrt_logp_grad_dev(bdrt_problem *p, const double *d_theta, const int *d_spec, int B, int jacobian, double *d_lp,
@@ -664,16 +648,14 @@ int bdrt_logp_grad(bdrt_problem *p, const double *theta, const int *spec, int B,
     int rc;
     if ((rc = check_spec(P, spec, B))) return rc;
     if ((rc = P.ensure_scratch((size_t)B))) return rc;
-    const size_t nb = (size_t)B * P.dev.D * sizeof(double);
-    BDRT_HIP(hipMemcpyAsync(P.d_theta, theta, nb, hipMemcpyHostToDevice, P.stream));
-    if (spec) BDRT_HIP(hipMemcpyAsync(P.d_spec, spec, (size_t)B * sizeof(int), hipMemcpyHostToDevice, P.stream));
-    rc = launch_logp_grad_few(&P, P.d_theta, spec ? P.d_spec : nullptr, B, jacobian, P.d_lp, grad ? P.d_grad : nullptr, P.stream);
+    const size_t n = (size_t)B * P.dev.D;
+    const int *d_spec = spec ? P.d_spec.p : nullptr;
+    double *d_grad = grad ? P.d_grad.p : nullptr;
+    if (upload(P.d_theta.p, theta, n, P.stream) || (spec && upload(P.d_spec.p, spec, (size_t)B, P.stream))) return -10;
+    rc = launch_logp_grad_few(&P, P.d_theta, d_spec, B, jacobian, P.d_lp, d_grad, P.stream);
     if (rc < 0) return rc;
-    if (rc > 0 && (rc = launch_logp_grad(&P, P.d_theta, spec ? P.d_spec : nullptr, B, jacobian, P.d_lp, grad ? P.d_grad : nullptr,
-                                         nullptr, nullptr, nullptr, P.stream)))
-        return rc;
-    if (lp) BDRT_HIP(hipMemcpyAsync(lp, P.d_lp, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, P.stream));
-    if (grad) BDRT_HIP(hipMemcpyAsync(grad, P.d_grad, nb, hipMemcpyDeviceToHost, P.stream));
+    if (rc > 0 && (rc = launch_logp_grad(&P, P.d_theta, d_spec, B, jacobian, P.d_lp, d_grad, nullptr, nullptr, nullptr, P.stream))) return rc;
+    if ((lp && download(lp, P.d_lp.p, (size_t)B, P.stream)) || (grad && download(grad, P.d_grad.p, n, P.stream))) return -10;
     BDRT_HIP(hipStreamSynchronize(P.stream));
     return 0;
 }
@@ -687,22 +669,18 @@ int bdrt_transformed(bdrt_problem *p, const double *theta, const int *spec, int 
     int rc;
     if ((rc = check_spec(P, spec, B))) return rc;
     if ((rc = P.ensure_scratch((size_t)B))) return rc;
-    const size_t nb = (size_t)B * P.dev.D * sizeof(double), nz = (size_t)B * 2 * P.dev.nf * sizeof(double);
-    double *d_par = nullptr, *d_zh = nullptr, *d_sg = nullptr;
-    BDRT_HIP(hipMalloc((void **)&d_par, nb));
-    BDRT_HIP(hipMalloc((void **)&d_zh, nz));
-    BDRT_HIP(hipMalloc((void **)&d_sg, nz));
-    BDRT_HIP(hipMemcpyAsync(P.d_theta, theta, nb, hipMemcpyHostToDevice, P.stream));
-    if (spec) BDRT_HIP(hipMemcpyAsync(P.d_spec, spec, (size_t)B * sizeof(int), hipMemcpyHostToDevice, P.stream));
-    rc = launch_logp_grad(&P, P.d_theta, spec ? P.d_spec : nullptr, B, 0, P.d_lp, nullptr, d_par, d_zh, d_sg, P.stream);
-    if (rc == 0) {
-        if (params) hipMemcpyAsync(params, d_par, nb, hipMemcpyDeviceToHost, P.stream);
-        if (Z_hat) hipMemcpyAsync(Z_hat, d_zh, nz, hipMemcpyDeviceToHost, P.stream);
-        if (sigma_tot) hipMemcpyAsync(sigma_tot, d_sg, nz, hipMemcpyDeviceToHost, P.stream);
-        if (hipStreamSynchronize(P.stream) != hipSuccess) { set_error("bdrt_transformed: sync failed"); rc = -10; }
-    }
-    hipFree(d_par); hipFree(d_zh); hipFree(d_sg);
-    return rc;
+    const size_t n = (size_t)B * P.dev.D, nz = (size_t)B * 2 * P.dev.nf;
+    DevBuf<double> d_par, d_zh, d_sg;
+    BDRT_HIP(d_par.alloc(n));
+    BDRT_HIP(d_zh.alloc(nz));
+    BDRT_HIP(d_sg.alloc(nz));
+    if (upload(P.d_theta.p, theta, n, P.stream) || (spec && upload(P.d_spec.p, spec, (size_t)B, P.stream))) return -10;
+    if ((rc = launch_logp_grad(&P, P.d_theta, spec ? P.d_spec.p : nullptr, B, 0, P.d_lp, nullptr, d_par, d_zh, d_sg, P.stream))) return rc;
+    if ((params && download(params, d_par.p, n, P.stream)) || (Z_hat && download(Z_hat, d_zh.p, nz, P.stream)) ||
+        (sigma_tot && download(sigma_tot, d_sg.p, nz, P.stream)))
+        return -10;
+    BDRT_HIP(hipStreamSynchronize(P.stream));      // (before the three buffers go: the copies read them)
+    return 0;
 }
 
 }  // extern "C"

@@ -118,7 +118,7 @@ __device__ inline bool chol_blocked(double *M, int Dp, double *lds, NewtonProf &
             row[j] = lij;
 #pragma unroll
             for (int k = j + 1; k < 16; ++k) {
-                const double lkj = bcast_lane(lij, k);                // L[k][j], owned by lane k
+                const double lkj = bcast_lane(lij, k);                // L[k][j], held by lane k
                 row[k] -= (i > j && k <= i) ? lij * lkj : 0.0;
             }
         }
@@ -677,87 +677,82 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
     const int D = P.dev.D, Dp = (D + 15) & ~15;
     BDRT_HIP(hipSetDevice(P.device));
     const auto t_host0 = std::chrono::steady_clock::now();
-    std::vector<void *> owned;
-    auto cleanup = [&]() { for (void *p : owned) hipFree(p); };
-#define NW_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    auto alloc = [&](size_t bytes, void **d) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes ? bytes : 8);
-        if (e == hipSuccess) owned.push_back(*d);
-        return e;
-    };
     NewtonBufs b;
     b.D = D; b.Dp = Dp;
-    const size_t nD = (size_t)n_fits * D * sizeof(double);
-    NW_HIP(alloc(nD, (void **)&b.x)); NW_HIP(alloc(nD, (void **)&b.g)); NW_HIP(alloc(NW_ATT * nD, (void **)&b.s));
-    NW_HIP(alloc(NW_ATT * nD, (void **)&b.xt)); NW_HIP(alloc(nD * NW_TRY, (void **)&b.gt)); NW_HIP(alloc(nD, (void **)&b.hstep));
-    NW_HIP(alloc((size_t)n_fits * NW_ATT * sizeof(NewtonAttempt), (void **)&b.att));
-    NW_HIP(hipMemsetAsync(b.att, 0, (size_t)n_fits * NW_ATT * sizeof(NewtonAttempt), P.stream));
-    NW_HIP(alloc((size_t)n_fits * Dp * Dp * sizeof(double), (void **)&b.H));
-    NW_HIP(alloc((size_t)n_fits * Dp * Dp * sizeof(double), (void **)&b.M));
+    const size_t nD = (size_t)n_fits * D, nM = (size_t)n_fits * Dp * Dp;
+    DevBuf<double> x, g, s, xt, gt, hstep, H, M, M2, probes, pgrad, plp, hws, lpt;
+    DevBuf<NewtonAttempt> att;
+    DevBuf<NewtonState> dst;
+    DevBuf<long long> prof;
+    DevBuf<int> active, spec1, specp, fspec;
+    BDRT_HIP(x.alloc(nD)); BDRT_HIP(g.alloc(nD)); BDRT_HIP(s.alloc(NW_ATT * nD));
+    BDRT_HIP(xt.alloc(NW_ATT * nD)); BDRT_HIP(gt.alloc(nD * NW_TRY)); BDRT_HIP(hstep.alloc(nD));
+    BDRT_HIP(att.alloc((size_t)n_fits * NW_ATT));
+    BDRT_HIP(hipMemsetAsync(att, 0, (size_t)n_fits * NW_ATT * sizeof(NewtonAttempt), P.stream));
+    BDRT_HIP(H.alloc(nM));
+    BDRT_HIP(M.alloc(nM));
     // the speculative factorisations (newton_solve_kernel) need matrices of their own: allocated while they stay below 2 GB (a 512-spectrum batch with them -- 2.3 GB of hipMalloc -- was 0.31 -> 0.38 s), used in the
     // launches that have the workgroups to spare (BDRT_NEWTON_SPEC=0: never)
-    b.M2 = nullptr;
     int n_cu = 0;
-    NW_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P.device));
+    BDRT_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P.device));
     const char *spec_env = getenv("BDRT_NEWTON_SPEC");
-    if (!(spec_env && spec_env[0] == '0') && (size_t)n_fits * (NW_ATT - 1) * Dp * Dp * sizeof(double) <= ((size_t)2 << 30))
-        NW_HIP(alloc((size_t)n_fits * (NW_ATT - 1) * Dp * Dp * sizeof(double), (void **)&b.M2));
+    if (!(spec_env && spec_env[0] == '0') && (NW_ATT - 1) * nM * sizeof(double) <= ((size_t)2 << 30))
+        BDRT_HIP(M2.alloc((NW_ATT - 1) * nM));
     // closed-form Hessian where the model has one (BDRT_NEWTON_FD=1: central differences of the gradient as in rounds 1-5)
     const char *fd_env = getenv("BDRT_NEWTON_FD");
     b.analytic = (hess_analytic_ok(P.dev) && !(fd_env && fd_env[0] == '1')) ? 1 : 0;
-    b.hws = nullptr; b.fspec = nullptr; b.dP = (const DevProblem *)P.d_dev;
+    b.dP = (const DevProblem *)P.d_dev;
     const HessLayout hlay(P.dev.nf, P.dev.blk[0].K);
     b.hl_total = hlay.total; b.hl_tz = hlay.tz; b.hl_act = hlay.act; b.hl_floor = hlay.h0 + 11; b.o_x = P.dev.blk[0].o_x; b.Kx = P.dev.blk[0].K;
     const char *lin_env = getenv("BDRT_NEWTON_LINEAR");      // 0: the coefficients stay on the log scale for the whole iteration
     b.lin_ok = (b.analytic && P.dev.blk[0].is_pos && !(lin_env && lin_env[0] == '0')) ? 1 : 0;
     if (b.analytic) {
         // (the probe buffer only carries the trial points of a round)
-        NW_HIP(alloc((size_t)n_fits * NW_TRY * D * sizeof(double), (void **)&b.probes));
-        b.pgrad = nullptr; b.plp = nullptr;
-        NW_HIP(alloc((size_t)n_fits * hlay.total * sizeof(double), (void **)&b.hws));
+        BDRT_HIP(probes.alloc(nD * NW_TRY));
+        BDRT_HIP(hws.alloc((size_t)n_fits * hlay.total));
     } else {
-        NW_HIP(alloc((size_t)n_fits * 2 * D * D * sizeof(double), (void **)&b.probes));
-        NW_HIP(alloc((size_t)n_fits * 2 * D * D * sizeof(double), (void **)&b.pgrad));
-        NW_HIP(alloc((size_t)n_fits * 2 * D * sizeof(double), (void **)&b.plp));
+        BDRT_HIP(probes.alloc(2 * nD * D));
+        BDRT_HIP(pgrad.alloc(2 * nD * D));
+        BDRT_HIP(plp.alloc(2 * nD));
     }
-    NW_HIP(alloc((size_t)n_fits * sizeof(NewtonState), (void **)&b.st));
-    b.prof = nullptr;
+    BDRT_HIP(dst.alloc((size_t)n_fits));
     const char *prof_env = getenv("BDRT_NEWTON_PROF");
     if (prof_env && prof_env[0] == '1') {
-        NW_HIP(alloc(NP_COUNT * sizeof(long long), (void **)&b.prof));
-        NW_HIP(hipMemset(b.prof, 0, NP_COUNT * sizeof(long long)));
-        NW_HIP(hipStreamSynchronize(nullptr));          // the fill is asynchronous; the kernels run on the problem's own stream
+        BDRT_HIP(prof.alloc(NP_COUNT));
+        BDRT_HIP(hipMemset(prof, 0, NP_COUNT * sizeof(long long)));
+        BDRT_HIP(hipStreamSynchronize(nullptr));          // the fill is asynchronous; the kernels run on the problem's own stream
     }
-    int *d_active = nullptr, *d_spec1 = nullptr, *d_specp = nullptr, *d_fspec = nullptr;
-    double *d_lpt = nullptr;
-    NW_HIP(alloc((size_t)n_fits * sizeof(int), (void **)&d_active));
-    NW_HIP(alloc((size_t)n_fits * NW_TRY * sizeof(int), (void **)&d_spec1));
-    NW_HIP(alloc((size_t)n_fits * (b.analytic ? 1 : 2 * D) * sizeof(int), (void **)&d_specp));
-    NW_HIP(alloc((size_t)n_fits * sizeof(int), (void **)&d_fspec));
-    b.fspec = d_fspec;
-    NW_HIP(alloc((size_t)n_fits * NW_TRY * sizeof(double), (void **)&d_lpt));
+    BDRT_HIP(active.alloc((size_t)n_fits));
+    BDRT_HIP(spec1.alloc((size_t)n_fits * NW_TRY));
+    BDRT_HIP(specp.alloc((size_t)n_fits * (b.analytic ? 1 : 2 * D)));
+    BDRT_HIP(fspec.alloc((size_t)n_fits));
+    BDRT_HIP(lpt.alloc((size_t)n_fits * NW_TRY));
+    // (an owner that was not allocated reads as nullptr: M2, pgrad, plp, hws, prof where the iteration does without them)
+    b.x = x; b.g = g; b.s = s; b.xt = xt; b.gt = gt; b.hstep = hstep; b.att = att; b.H = H; b.M = M; b.M2 = M2; b.probes = probes;
+    b.pgrad = pgrad; b.plp = plp; b.hws = hws; b.st = dst; b.prof = prof; b.fspec = fspec;
+    int *const d_active = active, *const d_spec1 = spec1, *const d_specp = specp;
+    double *const d_lpt = lpt;
     std::vector<NewtonState> hst((size_t)n_fits);
     for (auto &s : hst) { memset(&s, 0, sizeof(s)); s.lam = 1e-3; s.max_iter = max_iter; s.tol = tol; s.rc = 1; s.done = max_iter > 0 ? 0 : 1; }
-    NW_HIP(hipMemcpy(b.st, hst.data(), hst.size() * sizeof(NewtonState), hipMemcpyHostToDevice));
-    NW_HIP(hipMemcpy(b.x, x0, nD, hipMemcpyHostToDevice));
+    BDRT_HIP(hipMemcpy(b.st, hst.data(), hst.size() * sizeof(NewtonState), hipMemcpyHostToDevice));
+    BDRT_HIP(hipMemcpy(b.x, x0, nD * sizeof(double), hipMemcpyHostToDevice));
     hipStream_t st = P.stream;
     const auto t_host1 = std::chrono::steady_clock::now();
     // evaluation at the start points
     std::vector<int> hspec((size_t)n_fits), hact((size_t)n_fits), hspecp, sp1((size_t)n_fits * NW_TRY);
     for (int i = 0; i < n_fits; ++i) hspec[i] = spec ? spec[i] : 0;
-    NW_HIP(hipMemcpyAsync(d_spec1, hspec.data(), (size_t)n_fits * sizeof(int), hipMemcpyHostToDevice, st));
-    NW_HIP(hipMemcpyAsync(d_fspec, hspec.data(), (size_t)n_fits * sizeof(int), hipMemcpyHostToDevice, st));
+    if (upload(d_spec1, hspec.data(), (size_t)n_fits, st) || upload(fspec.p, hspec.data(), (size_t)n_fits, st)) return -10;
     const size_t lds_prep = hess_prep_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double), lds_fill = hess_fill_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double);
     if (b.analytic) {
-        NW_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-        NW_HIP(hipFuncSetAttribute((const void *)newton_accept_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-        NW_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
+        BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+        BDRT_HIP(hipFuncSetAttribute((const void *)newton_accept_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+        BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
     }
     int rc;
-    if ((rc = launch_logp_grad(&P, b.x, d_spec1, n_fits, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) { cleanup(); return rc; }
+    if ((rc = launch_logp_grad(&P, b.x, d_spec1, n_fits, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
     hipLaunchKernelGGL(newton_init_kernel, dim3(n_fits), dim3(256), 0, st, b, n_fits, (const double *)d_lpt, (const double *)b.gt);
     const size_t lds_solve = ((size_t)Dp + 64 + 16 * 17 + 16 + (size_t)Dp * 17 + 2) * sizeof(double);
-    NW_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
+    BDRT_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
     // The sequence of launches of one Levenberg-Marquardt round does not depend on what the round decides (kernels skip the
     // fits that are done; a fit that keeps its Hessian after a rejected trial skips the probe writes and ignores the probe
     // gradients), so several rounds are enqueued back to back and the host reads the status records once per group.
@@ -772,8 +767,8 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
     std::vector<int> hact_prev;
     int group = rounds_per_sync;
     for (long long round = 0; round < max_rounds; round += group) {
-        NW_HIP(hipMemcpyAsync(hst.data(), b.st, hst.size() * sizeof(NewtonState), hipMemcpyDeviceToHost, st));
-        NW_HIP(hipStreamSynchronize(st));
+        if (download(hst.data(), b.st, hst.size(), st)) return -10;
+        BDRT_HIP(hipStreamSynchronize(st));
         int n_active = 0;
         double g_far = 0.0;                                    // (the fit that will finish last decides how long the iteration runs)
         for (int i = 0; i < n_fits; ++i) if (!hst[i].done) { hact[n_active++] = i; g_far = std::max(g_far, hst[i].grad_inf); }
@@ -786,14 +781,13 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
         if (n_active == 0) break;
         if ((int)hact_prev.size() != n_active || !std::equal(hact_prev.begin(), hact_prev.end(), hact.begin())) {
             hact_prev.assign(hact.begin(), hact.begin() + n_active);
-            NW_HIP(hipMemcpyAsync(d_active, hact.data(), (size_t)n_active * sizeof(int), hipMemcpyHostToDevice, st));
+            if (upload(d_active, hact.data(), (size_t)n_active, st)) return -10;
             if (!b.analytic) hspecp.resize((size_t)n_active * 2 * D);
             for (int a = 0; a < n_active; ++a) {
                 if (!b.analytic) std::fill(hspecp.begin() + (size_t)a * 2 * D, hspecp.begin() + (size_t)(a + 1) * 2 * D, hspec[hact[a]]);
                 for (int t = 0; t < NW_TRY; ++t) sp1[(size_t)a * NW_TRY + t] = hspec[hact[a]];
             }
-            if (!b.analytic) NW_HIP(hipMemcpyAsync(d_specp, hspecp.data(), hspecp.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            NW_HIP(hipMemcpyAsync(d_spec1, sp1.data(), (size_t)n_active * NW_TRY * sizeof(int), hipMemcpyHostToDevice, st));
+            if ((!b.analytic && upload(d_specp, hspecp.data(), hspecp.size(), st)) || upload(d_spec1, sp1.data(), (size_t)n_active * NW_TRY, st)) return -10;
         }
         const int natt = b.M2 ? std::max(1, std::min(NW_ATT, n_cu / n_active)) : 1;
         for (int r = 0; r < group; ++r) {
@@ -806,7 +800,7 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
                 hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, n_active), dim3(HP_NT), lds_fill, st, b, (const int *)d_active, n_active);
             } else {
                 hipLaunchKernelGGL(newton_probe_kernel, dim3(2 * D, n_active), dim3(128), 0, st, b, (const int *)d_active, n_active);
-                if ((rc = launch_logp_grad(&P, b.probes, d_specp, n_active * 2 * D, 0, b.plp, b.pgrad, nullptr, nullptr, nullptr, st))) { cleanup(); return rc; }
+                if ((rc = launch_logp_grad(&P, b.probes, d_specp, n_active * 2 * D, 0, b.plp, b.pgrad, nullptr, nullptr, nullptr, st))) return rc;
                 hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, n_active), dim3(256), 0, st, b, (const int *)d_active, n_active);
             }
             hipLaunchKernelGGL(newton_solve_kernel, dim3(n_active, natt), dim3(NW_NT), lds_solve, st, b, (const int *)d_active, n_active, natt);
@@ -815,8 +809,8 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
             // (the one-workgroup-per-point evaluator where the family has one: 8 us against the tile evaluator's 24 for the eight points of
             //  a two-start fit; the same evaluator for every batch size -- a fit's numbers do not depend on its batch)
             rc = trial_few ? launch_logp_grad_few(&P, b.probes, d_spec1, n_active * NW_TRY, 0, d_lpt, b.gt, st, 1) : 1;
-            if (rc < 0) { cleanup(); return rc; }
-            if (rc == 1 && (rc = launch_logp_grad(&P, b.probes, d_spec1, n_active * NW_TRY, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) { cleanup(); return rc; }
+            if (rc < 0) return rc;
+            if (rc == 1 && (rc = launch_logp_grad(&P, b.probes, d_spec1, n_active * NW_TRY, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
             if (b.analytic)
                 hipLaunchKernelGGL(newton_accept_prep_kernel, dim3(n_active), dim3(HP_NT), lds_prep, st, b, (const int *)d_active, n_active,
                                    (const double *)d_lpt, (const double *)b.probes);
@@ -824,11 +818,10 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
                 hipLaunchKernelGGL(newton_accept_kernel, dim3(n_active), dim3(256), 0, st, b, (const int *)d_active, n_active, (const double *)d_lpt,
                                    (const double *)b.probes);
         }
-        NW_HIP(hipGetLastError());
+        BDRT_HIP(hipGetLastError());
     }
-    NW_HIP(hipMemcpyAsync(hst.data(), b.st, hst.size() * sizeof(NewtonState), hipMemcpyDeviceToHost, st));
-    NW_HIP(hipMemcpyAsync(x_out, b.x, nD, hipMemcpyDeviceToHost, st));
-    NW_HIP(hipStreamSynchronize(st));
+    if (download(hst.data(), b.st, hst.size(), st) || download(x_out, b.x, nD, st)) return -10;
+    BDRT_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < n_fits; ++i) {
         if (lp_out) lp_out[i] = hst[i].lp;
         if (ginf_out) ginf_out[i] = hst[i].grad_inf;
@@ -838,7 +831,7 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
     }
     if (b.prof) {
         long long hp[NP_COUNT];
-        NW_HIP(hipMemcpy(hp, b.prof, sizeof(hp), hipMemcpyDeviceToHost));
+        if (download(hp, b.prof, (size_t)NP_COUNT)) return -10;
         const double n = hp[NP_CALLS] ? (double)hp[NP_CALLS] : 1.0;
         fprintf(stderr, "[bdrt newton prof] D %d, %lld solve launches (workgroup 0); core cycles per launch: hessian %.0f, build %.0f, "
                 "chol diag %.0f / panel %.0f / trailing %.0f, solve %.0f, pred %.0f; wall %.1f us per launch\n", D, hp[NP_CALLS],
@@ -849,9 +842,9 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
         for (int k = NP_PREP0; k <= NP_PREP0 + 8; ++k) fprintf(stderr, " %.0f", hp[k] / n);
         fprintf(stderr, "; fill (row tile 8): stage %.0f, dense product %.0f, entries + stores %.0f; prep wall %.1f us\n", hp[NP_FILL0] / n, hp[NP_FILL0 + 1] / n, hp[NP_FILL0 + 2] / n, hp[NP_PREP0 + 9] / n / 100.0);
     }
-#undef NW_HIP
     const auto t_host2 = std::chrono::steady_clock::now();
-    cleanup();
+    // (what the profile times as "frees": the matrices and vectors go here and not at the closing brace)
+    for (DevBuf<double> *d : {&M2, &H, &M, &s, &xt, &gt, &probes, &pgrad, &hws, &x, &g, &hstep, &plp, &lpt}) d->reset();
     if (prof_env && prof_env[0] == '1') {
         const auto t_host3 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return (double)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
@@ -871,51 +864,37 @@ int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double 
     if (lin && !P.dev.blk[0].is_pos) return 1;
     const int D = P.dev.D, Dp = (D + 15) & ~15;
     BDRT_HIP(hipSetDevice(P.device));
-    std::vector<void *> owned;
-    auto cleanup = [&]() { for (void *p : owned) hipFree(p); };
-#define HP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    auto alloc = [&](size_t bytes, void **d) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes ? bytes : 8);
-        if (e == hipSuccess) owned.push_back(*d);
-        return e;
-    };
     NewtonBufs b;
     memset(&b, 0, sizeof(b));
     b.D = D; b.Dp = Dp; b.analytic = 1; b.dP = (const DevProblem *)P.d_dev;
     b.lin_ok = lin ? 1 : 0;
     const HessLayout hlay(P.dev.nf, P.dev.blk[0].K);
-    int *d_act = nullptr, *d_spec = nullptr;
-    double *d_lp = nullptr;
-    HP_HIP(alloc((size_t)D * sizeof(double), (void **)&b.x)); HP_HIP(alloc((size_t)D * sizeof(double), (void **)&b.g));
-    HP_HIP(alloc((size_t)Dp * Dp * sizeof(double), (void **)&b.H)); HP_HIP(alloc((size_t)Dp * Dp * sizeof(double), (void **)&b.M));
-    HP_HIP(alloc((size_t)hlay.total * sizeof(double), (void **)&b.hws)); HP_HIP(alloc(sizeof(NewtonState), (void **)&b.st));
-    HP_HIP(alloc(sizeof(int), (void **)&d_act)); HP_HIP(alloc(sizeof(int), (void **)&d_spec)); HP_HIP(alloc(sizeof(double), (void **)&d_lp));
-    b.fspec = d_spec;
+    DevBuf<double> x, g, H, M, hws, d_lp;
+    DevBuf<NewtonState> dst;
+    DevBuf<int> d_act, d_spec;
+    BDRT_HIP(x.alloc((size_t)D)); BDRT_HIP(g.alloc((size_t)D));
+    BDRT_HIP(H.alloc((size_t)Dp * Dp)); BDRT_HIP(M.alloc((size_t)Dp * Dp));
+    BDRT_HIP(hws.alloc((size_t)hlay.total)); BDRT_HIP(dst.alloc(1));
+    BDRT_HIP(d_act.alloc(1)); BDRT_HIP(d_spec.alloc(1)); BDRT_HIP(d_lp.alloc(1));
+    b.x = x; b.g = g; b.H = H; b.M = M; b.hws = hws; b.st = dst; b.fspec = d_spec;
     NewtonState hs;
     memset(&hs, 0, sizeof(hs)); hs.need_hess = 1; hs.lam = 0.0;
     const int zero = 0;
     hipStream_t st = P.stream;
-    HP_HIP(hipMemcpyAsync(b.st, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    HP_HIP(hipMemcpyAsync(b.x, theta, (size_t)D * sizeof(double), hipMemcpyHostToDevice, st));
-    HP_HIP(hipMemcpyAsync(d_act, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-    HP_HIP(hipMemcpyAsync(d_spec, &spec, sizeof(int), hipMemcpyHostToDevice, st));
-    int rc;
-    if ((rc = launch_logp_grad(&P, b.x, d_spec, 1, 0, d_lp, b.g, nullptr, nullptr, nullptr, st))) { cleanup(); return rc; }
+    if (upload(b.st, &hs, 1, st) || upload(b.x, theta, (size_t)D, st) || upload(d_act.p, &zero, 1, st) || upload(d_spec.p, &spec, 1, st)) return -10;
+    if (int rc = launch_logp_grad(&P, b.x, d_spec, 1, 0, d_lp, b.g, nullptr, nullptr, nullptr, st)) return rc;
     const size_t lds_prep = hess_prep_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double), lds_fill = hess_fill_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double);
-    HP_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-    HP_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
-    hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(1), dim3(HP_NT), lds_prep, st, b, (const int *)d_act, 1);
-    hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, 1), dim3(HP_NT), lds_fill, st, b, (const int *)d_act, 1);
-    HP_HIP(hipGetLastError());
+    BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+    BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
+    hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(1), dim3(HP_NT), lds_prep, st, b, (const int *)d_act.p, 1);
+    hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, 1), dim3(HP_NT), lds_fill, st, b, (const int *)d_act.p, 1);
+    BDRT_HIP(hipGetLastError());
     std::vector<double> hh((size_t)Dp * Dp);
-    HP_HIP(hipMemcpyAsync(hh.data(), b.H, hh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (held_out) HP_HIP(hipMemcpyAsync(held_out, b.hws + hlay.act, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, st));
-    HP_HIP(hipStreamSynchronize(st));
+    if (download(hh.data(), b.H, hh.size(), st) || (held_out && download(held_out, b.hws + hlay.act, (size_t)D, st))) return -10;
+    BDRT_HIP(hipStreamSynchronize(st));
     // (the kernels write the block lower triangle: mirror it)
     for (int i = 0; i < D; ++i)
         for (int j = 0; j <= i; ++j) H_out[(size_t)i * D + j] = H_out[(size_t)j * D + i] = hh[(size_t)i * Dp + j];
-#undef HP_HIP
-    cleanup();
     return 0;
 }
 

@@ -723,11 +723,10 @@ int lbfgs_device(Problem &P, const double *x0, const int *spec, int n, const bdr
     DevBuf<double> dx0, dxo, dgo, dwork;
     DevBuf<LbfgsDevReport> drep;
     DevBuf<int> dspec;
-    const size_t nb = (size_t)n * D * sizeof(double);
-    BDRT_HIP(dx0.alloc((size_t)n * D)); BDRT_HIP(dxo.alloc((size_t)n * D)); BDRT_HIP(dgo.alloc((size_t)n * D));
+    const size_t nD = (size_t)n * D;
+    if (upload(dx0, x0, nD) || (spec && upload(dspec, spec, (size_t)n))) return -10;
+    BDRT_HIP(dxo.alloc(nD)); BDRT_HIP(dgo.alloc(nD));
     BDRT_HIP(drep.alloc((size_t)n));
-    BDRT_HIP(hipMemcpy(dx0.p, x0, nb, hipMemcpyHostToDevice));
-    if (spec) { BDRT_HIP(dspec.alloc((size_t)n)); BDRT_HIP(hipMemcpy(dspec.p, spec, (size_t)n * sizeof(int), hipMemcpyHostToDevice)); }
     if (!solo) BDRT_HIP(dwork.alloc((size_t)n * LBFGS_WIDE_ROWS * DS));
     const long long cap = (long long)std::max(o.max_iter, 0) * 4 + 64;
     const int max_evals = (int)std::min<long long>(cap, 1LL << 30);
@@ -744,9 +743,7 @@ int lbfgs_device(Problem &P, const double *x0, const int *spec, int n, const bdr
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipStreamSynchronize(P.stream));
     std::vector<LbfgsDevReport> reps((size_t)n);
-    BDRT_HIP(hipMemcpy(reps.data(), drep.p, reps.size() * sizeof(LbfgsDevReport), hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(x_out, dxo.p, nb, hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(g_out, dgo.p, nb, hipMemcpyDeviceToHost));
+    if (download(reps.data(), drep.p, reps.size()) || download(x_out, dxo.p, nD) || download(g_out, dgo.p, nD)) return -10;
     for (int i = 0; i < n; ++i) { iters[i] = reps[i].iters; n_evals[i] = reps[i].n_evals; rc[i] = reps[i].rc; f[i] = reps[i].f; }
     return 0;
 }
@@ -862,10 +859,9 @@ static int debug_logp_grad(DebugEval which, const char *who, bdrt_problem *p, co
     DevBuf<double> dth, dlp, dg;
     DevBuf<int> dsp;
     const size_t n = (size_t)B * P.dev.D;
-    BDRT_HIP(dth.alloc(n)); BDRT_HIP(dg.alloc(n)); BDRT_HIP(dlp.alloc(B));
-    BDRT_HIP(hipMemcpy(dth, theta, n * sizeof(double), hipMemcpyHostToDevice));
+    if (upload(dth, theta, n) || (spec && upload(dsp, spec, (size_t)B))) return -10;
+    BDRT_HIP(dg.alloc(n)); BDRT_HIP(dlp.alloc(B));
     BDRT_HIP(hipMemset(dg, 0, n * sizeof(double)));
-    if (spec) { BDRT_HIP(dsp.alloc(B)); BDRT_HIP(hipMemcpy(dsp, spec, B * sizeof(int), hipMemcpyHostToDevice)); }
     if (which == DebugEval::solo) {
         const SoloGeom g = solo_geometry(P.dev.nf, P.dev.blk[0].K, P.dev.D);
         const size_t lds = solo_eval_lds_bytes(g);
@@ -882,8 +878,7 @@ static int debug_logp_grad(DebugEval which, const char *who, bdrt_problem *p, co
     }
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipDeviceSynchronize());
-    if (lp) BDRT_HIP(hipMemcpy(lp, dlp, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (grad) BDRT_HIP(hipMemcpy(grad, dg, n * sizeof(double), hipMemcpyDeviceToHost));
+    if ((lp && download(lp, dlp.p, (size_t)B)) || (grad && download(grad, dg.p, n))) return -10;
     return 0;
 }
 int bdrt_debug_solo_logp_grad(bdrt_problem *p, const double *theta, const int *spec, int B, int jacobian, double *lp, double *grad)
@@ -907,17 +902,15 @@ int bdrt_debug_leaf_joins(const double *lsw_sub, const double *w, const double *
     }
     DevBuf<double> d[6];
     DevBuf<int> di[2];
-    for (auto &q : d) BDRT_HIP(q.alloc((size_t)n));
-    for (auto &q : di) BDRT_HIP(q.alloc((size_t)n));
-    const double *in[3] = {lsw_sub, w, u};
-    for (int k = 0; k < 3; ++k) BDRT_HIP(hipMemcpy(d[k], in[k], (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    const size_t N = (size_t)n;
+    if (upload(d[0], lsw_sub, N) || upload(d[1], w, N) || upload(d[2], u, N)) return -10;
+    for (int k = 3; k < 6; ++k) BDRT_HIP(d[k].alloc(N));
+    for (auto &q : di) BDRT_HIP(q.alloc(N));
     hipLaunchKernelGGL(leaf_joins_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d[0].p, d[1].p, d[2].p, n, d[3].p, di[0].p, d[4].p, di[1].p, d[5].p);
     BDRT_HIP(hipGetLastError());
-    BDRT_HIP(hipMemcpy(lsw_dev, d[3], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(join_dev, di[0], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(lsw_ref, d[4], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(join_ref, di[1], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    BDRT_HIP(hipMemcpy(prob_ref, d[5], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (download(lsw_dev, d[3].p, N) || download(join_dev, di[0].p, N) || download(lsw_ref, d[4].p, N) || download(join_ref, di[1].p, N) ||
+        download(prob_ref, d[5].p, N))
+        return -10;
     return 0;
 }
 

@@ -659,41 +659,30 @@ int bdrt_qp_box_batch(const double *P, const double *q, const double *lo, int n,
     const bool in_lds = vec_bytes + msize * sizeof(double) <= 160 * 1024 - 2560;      // (2.5 KB of static LDS in chol_packed)
     const size_t lds = in_lds ? vec_bytes + msize * sizeof(double) : vec_bytes;
     if (lds + 2560 > 160 * 1024) { set_error("bdrt_qp_box_batch: n = %d too large", n); return -2; }      // (+ chol_packed's static LDS)
-    double *dP = nullptr, *dq = nullptr, *dlo = nullptr, *dx = nullptr, *dobj = nullptr, *dwork = nullptr;
-    int *dit = nullptr;
-    auto cleanup = [&]() { hipFree(dP); hipFree(dq); hipFree(dlo); hipFree(dx); hipFree(dobj); hipFree(dwork); hipFree(dit); };
-#define QP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    QP_HIP(hipMalloc((void **)&dP, (size_t)nb * n * n * sizeof(double)));
-    QP_HIP(hipMemcpy(dP, P, (size_t)nb * n * n * sizeof(double), hipMemcpyHostToDevice));
-    QP_HIP(hipMalloc((void **)&dq, (size_t)nb * n * sizeof(double)));
-    QP_HIP(hipMemcpy(dq, q, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice));
-    if (lo) {
-        QP_HIP(hipMalloc((void **)&dlo, (size_t)n * sizeof(double)));
-        QP_HIP(hipMemcpy(dlo, lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    }
-    QP_HIP(hipMalloc((void **)&dx, (size_t)nb * n * sizeof(double)));
-    QP_HIP(hipMalloc((void **)&dobj, (size_t)nb * sizeof(double)));
-    QP_HIP(hipMalloc((void **)&dit, (size_t)nb * sizeof(int)));
-    if (!in_lds) QP_HIP(hipMalloc((void **)&dwork, (size_t)nb * msize * sizeof(double)));
+    DevBuf<double> dP, dq, dlo, dx, dobj, dwork;
+    DevBuf<int> dit;
+    if (upload(dP, P, (size_t)nb * n * n) || upload(dq, q, (size_t)nb * n) || (lo && upload(dlo, lo, (size_t)n))) return -10;
+    BDRT_HIP(dx.alloc((size_t)nb * n));
+    BDRT_HIP(dobj.alloc((size_t)nb));
+    BDRT_HIP(dit.alloc((size_t)nb));
+    if (!in_lds) BDRT_HIP(dwork.alloc((size_t)nb * msize));
     static LdsAttrCache attr_cache;
-    QP_HIP(attr_cache.ensure(lds, [&]() {
+    BDRT_HIP(attr_cache.ensure(lds, [&]() {
         hipError_t e = hipFuncSetAttribute((const void *)qp_box_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess)
             e = hipFuncSetAttribute((const void *)qp_box_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         return e;
     }));
     if (in_lds)
-        hipLaunchKernelGGL(qp_box_kernel<true>, dim3(nb), dim3(QP_NT), lds, 0, dP, dq, dlo, n, dx, dobj, dit, dwork);
+        hipLaunchKernelGGL(qp_box_kernel<true>, dim3(nb), dim3(QP_NT), lds, 0, dP.p, dq.p, dlo.p, n, dx.p, dobj.p, dit.p, dwork.p);
     else
-        hipLaunchKernelGGL(qp_box_kernel<false>, dim3(nb), dim3(QP_NT), lds, 0, dP, dq, dlo, n, dx, dobj, dit, dwork);
-    QP_HIP(hipGetLastError());
-    QP_HIP(hipDeviceSynchronize());
-    QP_HIP(hipMemcpy(x, dx, (size_t)nb * n * sizeof(double), hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(qp_box_kernel<false>, dim3(nb), dim3(QP_NT), lds, 0, dP.p, dq.p, dlo.p, n, dx.p, dobj.p, dit.p, dwork.p);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipDeviceSynchronize());
     std::vector<int> its(nb);
-    QP_HIP(hipMemcpy(its.data(), dit, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
-    if (primal_objective) QP_HIP(hipMemcpy(primal_objective, dobj, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
-#undef QP_HIP
-    cleanup();
+    if (download(x, dx.p, (size_t)nb * n) || download(its.data(), dit.p, (size_t)nb) ||
+        (primal_objective && download(primal_objective, dobj.p, (size_t)nb)))
+        return -10;
     int worst = 0;
     for (int b = 0; b < nb; ++b) {
         if (iterations) iterations[b] = its[b];
@@ -726,87 +715,71 @@ int bdrt_ridge_ex(const bdrt_ridge_options *opt, const unsigned char *zero_delta
     const bool in_lds = (vec + msize + extra) * sizeof(double) <= 160 * 1024 - 2560;
     const size_t lds = (vec + (in_lds ? msize : 0) + extra) * sizeof(double);
     if (lds + 2560 > 160 * 1024) { set_error("bdrt_ridge: n = %d too large", n); return -2; }      // (+ chol_packed's static LDS)
-    std::vector<void *> owned;
-    auto cleanup = [&]() { for (void *p : owned) hipFree(p); };
-#define RG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    auto up = [&](const void *h, size_t bytes, const void **d) -> hipError_t {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess) return e;
-        owned.push_back(p);
-        if (h) e = hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
-        *d = p;
-        return e;
-    };
+    // inputs: a fresh buffer each, filled from the host; outputs and work space: allocated only
+    DevBuf<double> dG, dqbase, dfb, dbase, dLs, dlo, dlam0, dlam0s, dbetas, dx0, dPwork, dMwork, dcoef, dlam, dcost, dfun, dhc, dhl, dhf, dhk;
+    DevBuf<int> dgsel, diters, dflags;
+    DevBuf<unsigned char> dzd;
+    // (every size is positive by the checks above -- n, nb, ng, max_iter >= 1 -- except that of Ls, which a caller may pass with
+    //  K == 0 where the kernel does not read it: one element then, the kernel's pointer stays non-null)
+    if (Ls && K == 0) BDRT_HIP(dLs.alloc(1));
+    if (upload(dG, G, (size_t)ng * n * n) || upload(dqbase, qbase, (size_t)ng * n) || upload(dgsel, gsel, (size_t)nb) ||
+        upload(dzd, zero_delta1_g, (size_t)ng) || upload(dfb, hl_fbeta_b, (size_t)nb) || upload(dbase, base, (size_t)3 * n * n) ||
+        (Ls && K != 0 && upload(dLs, Ls, (size_t)3 * K * n)) || (lo && upload(dlo, lo, (size_t)n)) ||
+        upload(dlam0, lambda0, (size_t)nb) || upload(dlam0s, lam0s, (size_t)nb * 3) || upload(dbetas, betas, (size_t)nb * 3) ||
+        (x0 && upload(dx0, x0, (size_t)nb * n)))
+        return -10;
+    const bool hist = hist_coef && hist_lam && hist_fun && hist_cost;
+    BDRT_HIP(dPwork.alloc((size_t)nb * n * n));
+    if (!in_lds) BDRT_HIP(dMwork.alloc((size_t)nb * msize));
+    BDRT_HIP(dcoef.alloc((size_t)nb * n));
+    BDRT_HIP(dlam.alloc((size_t)nb * 3 * n));
+    BDRT_HIP(dcost.alloc((size_t)nb));
+    BDRT_HIP(dfun.alloc((size_t)nb));
+    BDRT_HIP(diters.alloc((size_t)nb));
+    BDRT_HIP(dflags.alloc((size_t)nb));
+    if (hist) {
+        BDRT_HIP(dhc.alloc((size_t)nb * mi * n));
+        BDRT_HIP(dhl.alloc((size_t)nb * mi * 3 * n));
+        BDRT_HIP(dhf.alloc((size_t)nb * mi));
+        BDRT_HIP(dhk.alloc((size_t)nb * mi));
+        BDRT_HIP(hipMemset(dhf, 0, (size_t)nb * mi * sizeof(double)));
+        BDRT_HIP(hipMemset(dhk, 0, (size_t)nb * mi * sizeof(double)));
+    }
     RidgeArgs a;
     memset(&a, 0, sizeof(a));
     a.n = n; a.K = K; a.off = opt->off; a.penalty = opt->penalty; a.max_iter = mi; a.hyper_lambda = opt->hyper_lambda;
     a.xtol = opt->xtol;
     for (int o = 0; o < 3; ++o) a.reg_ord[o] = opt->reg_ord[o];
-    const void *d = nullptr;
-    RG_HIP(up(G, (size_t)ng * n * n * 8, &d)); a.G = (const double *)d;
-    RG_HIP(up(qbase, (size_t)ng * n * 8, &d)); a.qbase = (const double *)d;
-    RG_HIP(up(gsel, (size_t)nb * sizeof(int), &d)); a.gsel = (const int *)d;
-    RG_HIP(up(zero_delta1_g, (size_t)ng, &d)); a.zero_delta1_g = (const unsigned char *)d;
-    RG_HIP(up(hl_fbeta_b, (size_t)nb * 8, &d)); a.hl_fbeta_b = (const double *)d;
-    RG_HIP(up(base, (size_t)3 * n * n * 8, &d)); a.base = (const double *)d;
-    if (Ls) { RG_HIP(up(Ls, (size_t)3 * K * n * 8, &d)); a.Ls = (const double *)d; }
-    if (lo) { RG_HIP(up(lo, (size_t)n * 8, &d)); a.lo = (const double *)d; }
-    RG_HIP(up(lambda0, (size_t)nb * 8, &d)); a.lambda0 = (const double *)d;
-    RG_HIP(up(lam0s, (size_t)nb * 3 * 8, &d)); a.lam0s = (const double *)d;
-    RG_HIP(up(betas, (size_t)nb * 3 * 8, &d)); a.betas = (const double *)d;
-    if (x0) { RG_HIP(up(x0, (size_t)nb * n * 8, &d)); a.x0 = (const double *)d; }
-    RG_HIP(up(nullptr, (size_t)nb * n * n * 8, &d)); a.Pwork = (double *)d;
-    if (!in_lds) { RG_HIP(up(nullptr, (size_t)nb * msize * 8, &d)); a.Mwork = (double *)d; }
-    RG_HIP(up(nullptr, (size_t)nb * n * 8, &d)); a.coef = (double *)d;
-    RG_HIP(up(nullptr, (size_t)nb * 3 * n * 8, &d)); a.lam = (double *)d;
-    RG_HIP(up(nullptr, (size_t)nb * 8, &d)); a.cost = (double *)d;
-    RG_HIP(up(nullptr, (size_t)nb * 8, &d)); a.fun = (double *)d;
-    RG_HIP(up(nullptr, (size_t)nb * sizeof(int), &d)); a.iters = (int *)d;
-    RG_HIP(up(nullptr, (size_t)nb * sizeof(int), &d)); a.flags = (int *)d;
-    if (hist_coef && hist_lam && hist_fun && hist_cost) {
-        RG_HIP(up(nullptr, (size_t)nb * mi * n * 8, &d)); a.hist_coef = (double *)d;
-        RG_HIP(up(nullptr, (size_t)nb * mi * 3 * n * 8, &d)); a.hist_lam = (double *)d;
-        RG_HIP(up(nullptr, (size_t)nb * mi * 8, &d)); a.hist_fun = (double *)d;
-        RG_HIP(up(nullptr, (size_t)nb * mi * 8, &d)); a.hist_cost = (double *)d;
-        RG_HIP(hipMemset(a.hist_fun, 0, (size_t)nb * mi * 8));
-        RG_HIP(hipMemset(a.hist_cost, 0, (size_t)nb * mi * 8));
-    }
+    a.G = dG; a.qbase = dqbase; a.gsel = dgsel; a.zero_delta1_g = dzd; a.hl_fbeta_b = dfb; a.base = dbase; a.Ls = dLs; a.lo = dlo;
+    a.lambda0 = dlam0; a.lam0s = dlam0s; a.betas = dbetas; a.x0 = dx0; a.Pwork = dPwork; a.Mwork = dMwork; a.coef = dcoef; a.lam = dlam;
+    a.cost = dcost; a.fun = dfun; a.iters = diters; a.flags = dflags; a.hist_coef = dhc; a.hist_lam = dhl; a.hist_fun = dhf; a.hist_cost = dhk;
     static LdsAttrCache attr_cache;
-    RG_HIP(attr_cache.ensure(lds, [&]() {
+    BDRT_HIP(attr_cache.ensure(lds, [&]() {
         hipError_t e = hipFuncSetAttribute((const void *)ridge_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess)
             e = hipFuncSetAttribute((const void *)ridge_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         return e;
     }));
-    { const int on = getenv("BDRT_QP_PROF") ? 1 : 0; static int was = 0; if (on != was) { RG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_qp_prof_on), &on, sizeof(on))); was = on; } }
+    { const int on = getenv("BDRT_QP_PROF") ? 1 : 0; static int was = 0; if (on != was) { BDRT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_qp_prof_on), &on, sizeof(on))); was = on; } }
     if (in_lds) hipLaunchKernelGGL(ridge_kernel<true>, dim3(nb), dim3(QP_NT), lds, 0, a);
     else hipLaunchKernelGGL(ridge_kernel<false>, dim3(nb), dim3(QP_NT), lds, 0, a);
-    RG_HIP(hipGetLastError());
-    RG_HIP(hipDeviceSynchronize());
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipDeviceSynchronize());
     if (getenv("BDRT_QP_PROF")) {
         long long h[8] = {0}, z[8] = {0};
-        RG_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_qp_prof), sizeof(h)));
-        RG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_qp_prof), z, sizeof(z)));
+        BDRT_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_qp_prof), sizeof(h)));
+        BDRT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_qp_prof), z, sizeof(z)));
         fprintf(stderr, "[bdrt qp prof] n %d, fit 0: %lld interior-point iterations; core cycles: form KKT %lld, factor %lld (diagonal blocks %lld, panels %lld, trailing %lld), triangular solves %lld, other %lld\n",
                 n, h[4], h[0], h[1], h[5], h[6], h[7], h[2], h[3]);
     }
-    RG_HIP(hipMemcpy(coef, a.coef, (size_t)nb * n * 8, hipMemcpyDeviceToHost));
-    if (lam) RG_HIP(hipMemcpy(lam, a.lam, (size_t)nb * 3 * n * 8, hipMemcpyDeviceToHost));
-    if (cost) RG_HIP(hipMemcpy(cost, a.cost, (size_t)nb * 8, hipMemcpyDeviceToHost));
-    if (fun) RG_HIP(hipMemcpy(fun, a.fun, (size_t)nb * 8, hipMemcpyDeviceToHost));
     std::vector<int> hfl(nb);
-    RG_HIP(hipMemcpy(hfl.data(), a.flags, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
-    if (iters) RG_HIP(hipMemcpy(iters, a.iters, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
+    if (download(coef, dcoef.p, (size_t)nb * n) || (lam && download(lam, dlam.p, (size_t)nb * 3 * n)) || (cost && download(cost, dcost.p, (size_t)nb)) ||
+        (fun && download(fun, dfun.p, (size_t)nb)) || download(hfl.data(), dflags.p, (size_t)nb) || (iters && download(iters, diters.p, (size_t)nb)))
+        return -10;
     if (flags) memcpy(flags, hfl.data(), (size_t)nb * sizeof(int));
-    if (a.hist_coef) {
-        RG_HIP(hipMemcpy(hist_coef, a.hist_coef, (size_t)nb * mi * n * 8, hipMemcpyDeviceToHost));
-        RG_HIP(hipMemcpy(hist_lam, a.hist_lam, (size_t)nb * mi * 3 * n * 8, hipMemcpyDeviceToHost));
-        RG_HIP(hipMemcpy(hist_fun, a.hist_fun, (size_t)nb * mi * 8, hipMemcpyDeviceToHost));
-        RG_HIP(hipMemcpy(hist_cost, a.hist_cost, (size_t)nb * mi * 8, hipMemcpyDeviceToHost));
-    }
-#undef RG_HIP
-    cleanup();
+    if (hist && (download(hist_coef, dhc.p, (size_t)nb * mi * n) || download(hist_lam, dhl.p, (size_t)nb * mi * 3 * n) ||
+                 download(hist_fun, dhf.p, (size_t)nb * mi) || download(hist_cost, dhk.p, (size_t)nb * mi)))
+        return -10;
     for (int b = 0; b < nb; ++b)
         if (hfl[b] == -3) { set_error("bdrt_ridge: KKT matrix of fit %d not positive definite", b); return -3; }
     return 0;

@@ -99,36 +99,24 @@ int bdrt_gram(const double *WA, const double *WZ, int nrows, int n, const double
 {
     if (!WA || nrows < 1 || n < 1 || (!P && !q) || (q && !WZ)) { set_error("bdrt_gram: bad arguments"); return -1; }
     bind_process_device();
-    double *dWA = nullptr, *dWZ = nullptr, *dL2 = nullptr, *dL1 = nullptr, *dP = nullptr, *dq = nullptr;
-    auto cleanup = [&]() { hipFree(dWA); hipFree(dWZ); hipFree(dL2); hipFree(dL1); hipFree(dP); hipFree(dq); };
-#define GR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    GR_HIP(hipMalloc((void **)&dWA, (size_t)nrows * n * sizeof(double)));
-    GR_HIP(hipMemcpy(dWA, WA, (size_t)nrows * n * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> dWA, dWZ, dL2, dL1, dP, dq;
+    if (upload(dWA, WA, (size_t)nrows * n)) return -10;
     if (P) {
-        GR_HIP(hipMalloc((void **)&dP, (size_t)n * n * sizeof(double)));
-        if (L2mat) {
-            GR_HIP(hipMalloc((void **)&dL2, (size_t)n * n * sizeof(double)));
-            GR_HIP(hipMemcpy(dL2, L2mat, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
-        }
+        BDRT_HIP(dP.alloc((size_t)n * n));
+        if (L2mat && upload(dL2, L2mat, (size_t)n * n)) return -10;
         const int tiles = (n + 15) / 16;
-        hipLaunchKernelGGL(gram_kernel, dim3(tiles, tiles), dim3(64), 0, 0, dWA, nrows, n, dL2, dP);
-        GR_HIP(hipGetLastError());
-        GR_HIP(hipMemcpy(P, dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(gram_kernel, dim3(tiles, tiles), dim3(64), 0, 0, dWA.p, nrows, n, dL2.p, dP.p);
+        BDRT_HIP(hipGetLastError());
+        if (download(P, dP.p, (size_t)n * n)) return -10;
     }
     if (q) {
-        GR_HIP(hipMalloc((void **)&dWZ, (size_t)nrows * sizeof(double)));
-        GR_HIP(hipMemcpy(dWZ, WZ, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice));
-        GR_HIP(hipMalloc((void **)&dq, (size_t)n * sizeof(double)));
-        if (L1vec) {
-            GR_HIP(hipMalloc((void **)&dL1, (size_t)n * sizeof(double)));
-            GR_HIP(hipMemcpy(dL1, L1vec, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        }
-        hipLaunchKernelGGL(gram_q_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dWA, dWZ, nrows, n, dL1, dq);
-        GR_HIP(hipGetLastError());
-        GR_HIP(hipMemcpy(q, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        if (upload(dWZ, WZ, (size_t)nrows)) return -10;
+        BDRT_HIP(dq.alloc((size_t)n));
+        if (L1vec && upload(dL1, L1vec, (size_t)n)) return -10;
+        hipLaunchKernelGGL(gram_q_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dWA.p, dWZ.p, nrows, n, dL1.p, dq.p);
+        BDRT_HIP(hipGetLastError());
+        if (download(q, dq.p, (size_t)n)) return -10;
     }
-#undef GR_HIP
-    cleanup();
     return 0;
 }
 
@@ -137,32 +125,25 @@ int bdrt_gram_batch(const double *A, int R, int n, const double *w, const double
 {
     if (!A || !w || R < 1 || n < 1 || ng < 1 || ng > 65535 || (!G && !q) || (q && !t)) { set_error("bdrt_gram_batch: bad arguments"); return -1; }
     bind_process_device();
-    const size_t bA = (size_t)R * n * sizeof(double), bw = (size_t)ng * R * sizeof(double), bL1 = (size_t)n * sizeof(double);
-    const size_t bG = G ? (size_t)ng * n * n * sizeof(double) : 0, bq = q ? (size_t)ng * n * sizeof(double) : 0;
+    const size_t nA = (size_t)R * n, nw = (size_t)ng * R, nG = G ? (size_t)ng * n * n : 0, nq = q ? (size_t)ng * n : 0;
     // one allocation for the whole call: [A | w | t | L1 | G | q]
-    char *dbuf = nullptr;
-    auto cleanup = [&]() { hipFree(dbuf); };
-#define GB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return -10; } } while (0)
-    GB_HIP(hipMalloc((void **)&dbuf, bA + 2 * bw + bL1 + bG + bq));
-    double *dA = (double *)dbuf, *dw = (double *)(dbuf + bA), *dt = (double *)(dbuf + bA + bw), *dL1 = (double *)(dbuf + bA + 2 * bw);
-    double *dG = (double *)(dbuf + bA + 2 * bw + bL1), *dq = (double *)(dbuf + bA + 2 * bw + bL1 + bG);
-    GB_HIP(hipMemcpy(dA, A, bA, hipMemcpyHostToDevice));
-    GB_HIP(hipMemcpy(dw, w, bw, hipMemcpyHostToDevice));
+    DevBuf<double> dbuf;
+    BDRT_HIP(dbuf.alloc(nA + 2 * nw + n + nG + nq));
+    double *dA = dbuf, *dw = dA + nA, *dt = dw + nw, *dL1 = dt + nw, *dG = dL1 + n, *dq = dG + nG;
+    BDRT_HIP(hipMemcpy(dA, A, nA * sizeof(double), hipMemcpyHostToDevice));
+    BDRT_HIP(hipMemcpy(dw, w, nw * sizeof(double), hipMemcpyHostToDevice));
     if (G) {
         const int tiles = (n + 15) / 16;
         hipLaunchKernelGGL(gram_batch_kernel, dim3(tiles, tiles, ng), dim3(64), 0, 0, dA, dw, R, n, dG);
-        GB_HIP(hipGetLastError());
+        BDRT_HIP(hipGetLastError());
     }
     if (q) {
-        GB_HIP(hipMemcpy(dt, t, bw, hipMemcpyHostToDevice));
-        if (L1vec) GB_HIP(hipMemcpy(dL1, L1vec, bL1, hipMemcpyHostToDevice));
+        BDRT_HIP(hipMemcpy(dt, t, nw * sizeof(double), hipMemcpyHostToDevice));
+        if (L1vec) BDRT_HIP(hipMemcpy(dL1, L1vec, n * sizeof(double), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(gram_q_batch_kernel, dim3((n + 63) / 64, ng), dim3(64), 0, 0, dA, dw, dt, R, n, L1vec ? dL1 : nullptr, dq);
-        GB_HIP(hipGetLastError());
+        BDRT_HIP(hipGetLastError());
     }
-    if (G) GB_HIP(hipMemcpy(G, dG, bG, hipMemcpyDeviceToHost));
-    if (q) GB_HIP(hipMemcpy(q, dq, bq, hipMemcpyDeviceToHost));
-#undef GB_HIP
-    cleanup();
+    if ((G && download(G, dG, nG)) || (q && download(q, dq, nq))) return -10;
     return 0;
 }
 
