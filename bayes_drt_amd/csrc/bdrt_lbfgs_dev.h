@@ -84,11 +84,10 @@ __global__ __launch_bounds__(SOLO_NT) void lbfgs_kernel(const DevProblem *__rest
     DevVecs<NE> &v = c.v;
     v.tid = tid; v.lane = tid & 63; v.wave = tid >> 6; v.rslot = 0;
     double *TH, *GR, *lpv;
-    SoloEvalRegs ers;
-    Wide1Regs erw;
+    SoloEvalRegs ers, erw;
     if constexpr (WIDE) {
         wide1_init(P, G, smem, tid);
-        erw = wide1_setup(P, G, sp, tid);
+        erw = solo_eval_setup(P, G.g, sp, tid);
         double *w = work + (size_t)fit * LBFGS_WIDE_ROWS * DS;
         TH = w; GR = w + DS; v.hist = w + 2 * (size_t)DS; v.stride = DS;
         lpv = smem + G.total; v.red = smem + G.o_red;

@@ -443,7 +443,7 @@ __global__ __launch_bounds__(SOLO_NT) void nuts_wide1_kernel(const DevProblem *_
         for (int j = tid; j < DS; j += SOLO_NT) hot[(size_t)k * DS + j] = src[j];
     }
     __syncthreads();
-    const Wide1Regs er = wide1_setup(P, G, sts[0].spec, tid);
+    const SoloEvalRegs er = solo_eval_setup(P, G.g, sts[0].spec, tid);
     if (!sts[0].kicked) {
         // half kick + drift of the first evaluation of a freshly created sampler
         const int ph = sts[0].phase;
@@ -567,7 +567,7 @@ __global__ __launch_bounds__(SOLO_NT) void wide1_eval_kernel(const DevProblem *_
     const int tid = threadIdx.x;
     wide1_init(P, G, smem, tid);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {          // (a workgroup per point, or a grid-stride loop over the points)
-        const Wide1Regs er = wide1_setup(P, G, spec ? spec[b] : 0, tid);
+        const SoloEvalRegs er = solo_eval_setup(P, G.g, spec ? spec[b] : 0, tid);
         __syncthreads();
         wide1_eval(P, G, smem, theta + (size_t)b * P.D, grad + (size_t)b * P.D, lp + b, er, jacobian, tid);
     }

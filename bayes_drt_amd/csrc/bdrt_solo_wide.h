@@ -6,7 +6,7 @@
 // MFMA tile for one live column: ~60 us per leapfrog.  Here the evaluation is spread over the 512 threads the way
 // bdrt_solo.h does it -- A x and A^T g as Toeplitz products from the blocks' generators (every block of a log-uniform
 // grid is Toeplitz: the integrand depends on ln(omega_n tau_m) only), banded L as 13-tap convolutions -- block after block,
-// with the formulas of bdrt_tile_hw.h (Series / Parallel / Series-Parallel / Series-2Parallel model code, +- pos,
+// with the model terms of bdrt_model_terms.h (Series / Parallel / Series-Parallel / Series-2Parallel model code, +- pos,
 // +- outliers).  The chain's vectors stay in HBM (they do not fit in LDS at D = 818); everything after the evaluation is
 // the cooperative stage of bdrt_nuts_wide.h.
 //
@@ -57,25 +57,6 @@ inline bool wide1_capable(const DevProblem &P)
     return (size_t)wide1_geometry(P.nf, K, P.D, P.nblocks).total * sizeof(double) + 16384 <= 160 * 1024;
 }
 
-struct Wide1Regs {
-    double zre, zim, wn;      // measured spectrum of row n = tid (tid < nf)
-    int fpart, frg;           // forward product: m-part and 4-row group of this thread
-    int bpart, bmg;           // backward product: n-part and 4-column group of this thread
-};
-
-__device__ __forceinline__ Wide1Regs wide1_setup(const DevProblem &P, const Wide1Geom &G, int spec, int tid)
-{
-    const SoloGeom &g = G.g;
-    Wide1Regs er;
-    const int n = tid < g.nf ? tid : 0;
-    const double *Zm = P.Z + (size_t)spec * 2 * g.nf;
-    er.zre = Zm[n]; er.zim = Zm[g.nf + n]; er.wn = P.w[n];
-    const int pt = tid - g.FP0;
-    er.fpart = pt >= 0 ? pt / g.RG : g.NP; er.frg = pt - er.fpart * g.RG;
-    er.bpart = tid / g.MG; er.bmg = tid - er.bpart * g.MG;
-    return er;
-}
-
 // one-time LDS set-up: zero halos / pads, the generators of every block in swizzled order
 __device__ __forceinline__ void wide1_init(const DevProblem &P, const Wide1Geom &G, double *lds, int tid)
 {
@@ -84,7 +65,7 @@ __device__ __forceinline__ void wide1_init(const DevProblem &P, const Wide1Geom 
         lds[i] = (i >= G.o_us && i < G.o_us + g.XL) ? 1.0 : 0.0;
     for (int i = tid; i < G.total - G.o_zp; i += SOLO_NT) lds[G.o_zp + i] = 0.0;
     const int glen = g.nf + g.K - 1;
-    for (int i = tid; i < G.nb * 2 * 4 * g.GQ; i += SOLO_NT) {
+    for (int i = tid; i < G.nb * 2 * 4 * g.GQ; i += SOLO_NT) {                       // (the loop of solo_eval_init, over every block)
         const int blk = i / (2 * 4 * g.GQ), i2 = i - blk * 2 * 4 * g.GQ;
         const int h = i2 / (4 * g.GQ), r = i2 - h * 4 * g.GQ, rho = r / g.GQ, q = r - rho * g.GQ;
         const int e = 4 * q + rho;                                                   // logical index: n - m + S
@@ -128,7 +109,7 @@ __device__ __forceinline__ void wide1_dense_bwd(const double *__restrict__ Ad, i
 // log-posterior + gradient at theta (global row TH) -> gradient to the global row GR, lp to *lp_out (LDS or global).
 // All 512 threads call; ends with a __syncthreads().
 __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, double *lds, const double *__restrict__ TH,
-                                  double *__restrict__ GR, double *lp_out, const Wide1Regs &er, int jacobian, int tid,
+                                  double *__restrict__ GR, double *lp_out, const SoloEvalRegs &er, int jacobian, int tid,
                                   long long *prof = nullptr)
 {
     long long tprev = (prof && tid == 0) ? clock64() : 0;
@@ -151,7 +132,7 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
         const double st = TH[sj];
         sraw = lean_exp(st);
         scv[sidx] = sraw;
-        lp += (sidx < 6 ? -0.5 * sraw * sraw : -6.0 * st - 5.0 * lean_rcp(sraw)) + jac * st;
+        lp += (sidx < 6 ? raw_prior_lp(sraw) : strength_prior_lp(sraw, st)) + jac * st;
     }
     double xv[W1_MAXB], gupv[W1_MAXB];                     // x_k and d lp / d theta_ups_k of this thread's k, per block
     double xsum_p = 0.0;
@@ -178,20 +159,11 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
         }
     };
     auto conv_lt = [&](int b) {                            // sum_i L_i^T w_i of block b (threads CONV0 + k)
-        const DevBlock &B = P.blk[b];
         const int kc = tid - SOLO_CONV0;
-        if (kc >= 0 && kc < K) {
-            double gl = 0.0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double *wi = wr + i * g.XL;
-#pragma unroll
-                for (int d = 0; d < 2 * MAXBW + 1; ++d) gl = fma(B.T[i][d], wi[kc + 2 * MAXBW - d], gl);   // w_i[kc + MAXBW - d]
-            }
-            gls[b * g.XL + kc] = gl;
-        }
+        if (kc >= 0 && kc < K) gls[b * g.XL + kc] = solo_conv_lt(P.blk[b], wr, g.XL, kc);
     };
     auto sum_partials = [&](int n, double &yr, double &yi) {       // Y_b[n] from the partial sums of the current product
+        // (the batch of solo_eval at PB = 16; one function for both costs solo_eval's kernels scalar registers)
         const int st = 4 * g.RG;
         double r_[16], i_[16];
 #pragma unroll
@@ -235,31 +207,12 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
             }
             const double d0 = scv[6 + 3 * b], d1 = scv[7 + 3 * b], d2 = scv[8 + 3 * b];
             const double um2 = us[k], um1 = us[k + 1], up1 = us[k + 3], up2 = us[k + 4];
-            const double iu = lean_rcp(uu), iu2 = iu * iu;
-            const double q2 = d0 * v0 * v0 + d1 * v1 * v1 + d2 * v2 * v2;
-            const double ir = 0.15 * iu;                   // 1 / ups_raw
-            lp += -(tu + LOG_015) - 0.5 * q2 * iu2 - (P.ups_alpha + 1.0) * tu - P.ups_beta * ir + jac * tu;
-            sv0 = v0 * v0 * iu2; sv1 = v1 * v1 * iu2; sv2 = v2 * v2 * iu2;
-            double gu = -iu + q2 * iu2 * iu;
-            if (k >= 1 && k + 1 < K) {
-                const double du = 0.5 * (uu - 0.5 * (um1 + up1)) * iu;
-                lp += -0.5 * du * du;
-                gu += -du * 0.25 * (um1 + up1) * iu2;
-            }
-            if (k >= 2) {
-                const double i0 = lean_rcp(um1);
-                const double du = 0.5 * (um1 - 0.5 * (um2 + uu)) * i0;
-                gu += du * 0.25 * i0;
-            }
-            if (k + 2 < K) {
-                const double i0 = lean_rcp(up1);
-                const double du = 0.5 * (up1 - 0.5 * (uu + up2)) * i0;
-                gu += du * 0.25 * i0;
-            }
-            gupv[b] = uu * gu - (P.ups_alpha + 1.0) + P.ups_beta * ir + jac;
-            wr[MAXBW + k] = -d0 * v0 * iu2;
-            wr[g.XL + MAXBW + k] = -d1 * v1 * iu2;
-            wr[2 * g.XL + MAXBW + k] = -d2 * v2 * iu2;
+            const UpsPrior up = ups_prior_k(P, jac, v0, v1, v2, d0, d1, d2, tu, uu, um2, um1, up1, up2, k, K, lp);
+            sv0 = up.sv0; sv1 = up.sv1; sv2 = up.sv2;
+            gupv[b] = up.gup;
+            wr[MAXBW + k] = up.w0;
+            wr[g.XL + MAXBW + k] = up.w1;
+            wr[2 * g.XL + MAXBW + k] = up.w2;
         }
         if (wave < 3) {                                    // the K-threads live in waves 0..2 (K <= 192)
             // one butterfly for the three sums (sum32_by_lane: lane j of each half-wave ends with sum j), the halves meet in lanes 0..2
@@ -305,15 +258,11 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
                 if (b >= nb) break;
                 const double yr = yb[b * 2 * g.NFP + n], yi = yb[b * 2 * g.NFP + g.NFP + n];
                 if (!P.blk[b].is_parallel) { zr += yr; zi += yi; }
-                else {
-                    const double idn = lean_rcp(yr * yr + yi * yi);
-                    zr += yr * idn;                        // Z_hat_p = conj(Y) / |Y|^2 (Parallel_modelcode.txt:47)
-                    zi += -yi * idn;
-                }
+                else parallel_fwd(yr, yi, zr, zi);
             }
-            const double Rinf = 100.0 * scv[0], induc = scv[1] * P.induc_scale;
-            const double s_res = 0.05 * scv[2], a_p = 0.05 * scv[3], a_r = 0.05 * scv[4], a_i = 0.05 * scv[5];
-            zr += Rinf; zi += induc * er.wn;
+            const LikConsts lc = lik_consts(P, scv[0], scv[1], scv[2], scv[3], scv[4], scv[5]);
+            const double c0 = lc.c0, ap2 = lc.ap2, ar2 = lc.ar2, ai2 = lc.ai2;
+            zr += lc.Rinf; zi += lc.induc * er.wn;
             double so_re = 0.0, so_im = 0.0, r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
             if (P.outlier_mode) {
                 t0 = TH[P.o_so + n]; t1 = TH[P.o_so + nf + n];
@@ -321,8 +270,9 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
                 if (P.outlier_mode == 1) so_re = so_im = 0.05 * r0 * r1;
                 else { so_re = 0.05 * r0; so_im = 0.05 * r1; }
             }
-            const double c0 = P.sigma_min * P.sigma_min + s_res * s_res;
-            const double ap2 = a_p * a_p, ar2 = a_r * a_r, ai2 = a_i * a_i;
+            // (the text of lik_point, lik_sums and of the outlier model of bdrt_model_terms.h.  With them as calls this evaluator fuses
+            //  the products 0.5 e^2 w into the subtractions of lp, where it has always rounded them first, and adds jac to the outlier
+            //  gradients behind the choice of the mode instead of in one fma: other bits of lp and of the gradient)
             const double common = ar2 * zr * zr + ai2 * zi * zi;
             const double s2_re = c0 + ap2 * zr * zr + common + so_re * so_re;
             const double s2_im = c0 + ap2 * zi * zi + common + so_im * so_im;
@@ -377,16 +327,10 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
     if (sj >= 0) {
         double gsc;
         if (sidx < 6) {
-            const double t = ered[sidx] + ered[32 + sidx];
-            double dl;
-            if (sidx == 0) dl = 100.0 * t;
-            else if (sidx == 1) dl = P.induc_scale * t;
-            else dl = 0.05 * 2.0 * (0.05 * sraw) * t;
-            gsc = sraw * (dl - sraw) + jac;
+            gsc = scalar_grad(P, sidx, sraw, ered[sidx] + ered[32 + sidx], jac);
         } else {
             const int q = 8 + (sidx - 6);                  // slot 8 + 3 b + i
-            const double sv = ered[q] + ered[32 + q] + ered[64 + q];
-            gsc = -0.5 * sraw * sv - 6.0 + 5.0 * lean_rcp(sraw) + jac;
+            gsc = strength_grad(sraw, ered[q] + ered[32 + q] + ered[64 + q], jac);
         }
         GR[sj] = gsc;
     }
@@ -407,11 +351,8 @@ __device__ inline void wide1_eval(const DevProblem &P, const Wide1Geom &G, doubl
             double rr = gz[n], ri = gz[g.NFP + n];
             if (B.is_parallel) {
                 const double yr = yb[b * 2 * g.NFP + n], yi = yb[b * 2 * g.NFP + g.NFP + n];
-                const double dn = yr * yr + yi * yi, id2 = lean_rcp(dn * dn);
-                const double dd = (yi * yi - yr * yr) * id2, doff = 2.0 * yr * yi * id2;
-                const double gr_ = rr, gi_ = ri;
-                rr = (gr_ * dd + gi_ * doff) * B.x_scale;
-                ri = (-gr_ * doff + gi_ * dd) * B.x_scale;
+                parallel_bwd(yr, yi, rr, ri);
+                rr *= B.x_scale; ri *= B.x_scale;
             }
             rop[n] = rr; rop[g.NFP + n] = ri;
         }

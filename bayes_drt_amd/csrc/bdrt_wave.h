@@ -412,7 +412,7 @@ __device__ __forceinline__ int wave_slot_index(const DevProblem &P, int K, int u
 template <int KS, int NS, bool OM> constexpr int wave_slots() { return 2 * KS + 1 + (OM ? 2 * NS : 0); }
 
 // log-posterior + gradient of the chain at theta (registers, slot order above) -> gradient (registers), returns lp (uniform).
-// Formulas: bdrt_solo.h / bdrt_tile_s1.h (same model code, other thread mapping).  `jac`: 1.0 with the Jacobian of the
+// Model terms: bdrt_model_terms.h (the same model code as bdrt_solo.h, other thread mapping).  `jac`: 1.0 with the Jacobian of the
 // lower = 0 transforms (sampling), 0.0 without (optimisation).
 // OCC: waves per SIMD the instantiation is scheduled for.  2 (default): the kernel of a full CU (eight chains), bound by VALU issue.  1: at most four
 // chains on the CU -- nothing hides a wave's own LDS / scalar-load latency, so the products request their operands an iteration ahead
@@ -457,7 +457,7 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
     double sc[9];
     const double st = th[2 * KS];
     const double sraw = lean_exp(st);
-    lp += lane < 9 ? (lane < 6 ? -0.5 * sraw * sraw : -6.0 * st - 5.0 * lean_rcp(sraw)) + jac * st : 0.0;
+    lp += lane < 9 ? (lane < 6 ? raw_prior_lp(sraw) : strength_prior_lp(sraw, st)) + jac * st : 0.0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) sc[i] = wv_bcast(sraw, i);
     wv_sync();
@@ -562,6 +562,8 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
             const double ir = 0.15 * iu;                       // 1 / ups_raw
             double lpk = -(tu + LOG_015) - 0.5 * q2 * iu2 - (P.ups_alpha + 1.0) * tu - P.ups_beta * ir + jac * tu;
             double gu = -iu + q2 * iu2 * iu;
+            // (the ups prior of ups_prior_k, bdrt_model_terms.h, in this evaluator's own form; as a call shared with wave_eval_nb the
+            //  schedule for two waves per SIMD takes up to four more vector registers)
             // neighbour terms of the ups prior: centre k, and k as the right / left neighbour of the centres k - 1 / k + 1.  Every accumulation
             // is an explicit fma of the same operands in both schedules (OCC 1 and 2 give the same bits: chains change schedule between
             // launches when the number of live chains crosses four per CU).
@@ -620,10 +622,7 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
     double T[7];
     {
         double sR = 0, sL = 0, sH = 0, sHz2 = 0, sHzr2 = 0, sHzi2 = 0;
-        const double Rinf = 100.0 * sc[0], induc = sc[1] * P.induc_scale;
-        const double s_res = 0.05 * sc[2], a_p = 0.05 * sc[3], a_r = 0.05 * sc[4], a_i = 0.05 * sc[5];
-        const double c0 = P.sigma_min * P.sigma_min + s_res * s_res;
-        const double ap2 = a_p * a_p, ar2 = a_r * a_r, ai2 = a_i * a_i;
+        const LikConsts lc = lik_consts(P, sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int n = lane + 64 * s;
@@ -632,45 +631,38 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
             double zr = 0.0, zi = 0.0;
 #pragma unroll 1
             for (int p = 0; p < g.NP; ++p) { zr += zp[(size_t)(2 * p) * g.R4 + nn]; zi += zp[(size_t)(2 * p + 1) * g.R4 + nn]; }
-            zr += Rinf; zi += induc * er.wn[s];
-            const double common = ar2 * zr * zr + ai2 * zi * zi;
-            // outlier error model (formulas of bdrt_tile_hw.h): sigma_out enters the variances; its two parameters per row are this lane's
-            [[maybe_unused]] double so_re = 0.0, so_im = 0.0, r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
+            zr += lc.Rinf; zi += lc.induc * er.wn[s];
+            // outlier error model: sigma_out enters the variances; its two parameters per row are this lane's
+            [[maybe_unused]] OutlierSigma so = {0.0, 0.0};
+            [[maybe_unused]] double r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
             if constexpr (OM) {
                 t0 = th[2 * KS + 1 + s]; t1 = th[2 * KS + 1 + NS + s];
                 r0 = lean_exp(t0); r1 = lean_exp(t1);
-                if (P.outlier_mode == 1) so_re = so_im = 0.05 * r0 * r1;
-                else { so_re = 0.05 * r0; so_im = 0.05 * r1; }
+                so = outlier_sigma(P.outlier_mode, r0, r1);
             }
-            double s2_re = c0 + ap2 * zr * zr + common, s2_im = c0 + ap2 * zi * zi + common;
-            if constexpr (OM) { s2_re += so_re * so_re; s2_im += so_im * so_im; }
+            // (the text of lik_point and, below, of lik_sums of bdrt_model_terms.h: with either as a call one instantiation of the
+            //  evaluator's own kernel spills one more scalar register)
+            const double common = lc.ar2 * zr * zr + lc.ai2 * zi * zi;
+            double s2_re = lc.c0 + lc.ap2 * zr * zr + common, s2_im = lc.c0 + lc.ap2 * zi * zi + common;
+            if constexpr (OM) { s2_re += so.re * so.re; s2_im += so.im * so.im; }
             const double e_re = er.zre[s] - zr, e_im = er.zim[s] - zi;
             const double prod = s2_re * s2_im, ip = lean_rcp(prod);
             const double w_re = s2_im * ip, w_im = s2_re * ip;
             const double lpn = -0.5 * lean_log(prod) - 0.5 * e_re * e_re * w_re - 0.5 * e_im * e_im * w_im;
             const double h_re = -0.5 * w_re + 0.5 * e_re * e_re * w_re * w_re;
             const double h_im = -0.5 * w_im + 0.5 * e_im * e_im * w_im * w_im;
-            const double gzr = e_re * w_re + 2.0 * zr * (h_re * (ap2 + ar2) + h_im * ar2);
-            const double gzi = e_im * w_im + 2.0 * zi * (h_im * (ap2 + ai2) + h_re * ai2);
+            const double gzr = e_re * w_re + 2.0 * zr * (h_re * (lc.ap2 + lc.ar2) + h_im * lc.ar2);
+            const double gzi = e_im * w_im + 2.0 * zi * (h_im * (lc.ap2 + lc.ai2) + h_re * lc.ai2);
+            const LikPoint pt = {lpn, gzr, gzi, h_re, h_im};
             if constexpr (OM) {
-                double g0 = 0.0, g1 = 0.0, lpo = 0.0;
-                if (P.outlier_mode == 1) {
-                    const double dso = 2.0 * so_re * (h_re + h_im), ir1 = lean_rcp(r1);
-                    g0 = r0 * (0.05 * r1 * dso - P.so_lambda) + jac;
-                    g1 = 0.05 * r0 * r1 * dso - (P.so_alpha + 1.0) + P.so_beta * ir1 + jac;
-                    lpo = -P.so_lambda * r0 - (P.so_alpha + 1.0) * t1 - P.so_beta * ir1 + jac * (t0 + t1);
-                } else {
-                    g0 = r0 * (0.05 * 2.0 * so_re * h_re - P.so_lambda) + jac;
-                    g1 = r1 * (0.05 * 2.0 * so_im * h_im - P.so_lambda) + jac;
-                    lpo = -P.so_lambda * (r0 + r1) + jac * (t0 + t1);
-                }
-                gr[2 * KS + 1 + s] = nv ? g0 : 0.0; gr[2 * KS + 1 + NS + s] = nv ? g1 : 0.0;
-                lp += nv ? lpo : 0.0;
+                const OutlierTerms ot = outlier_terms(P, P.outlier_mode, jac, t0, t1, r0, r1, so, pt);
+                gr[2 * KS + 1 + s] = nv ? ot.g0 : 0.0; gr[2 * KS + 1 + NS + s] = nv ? ot.g1 : 0.0;
+                lp += nv ? ot.lp : 0.0;
             }
             if (nv) {                                          // (zeros from the set-up on [nf, NLP): the backward product's padding)
                 gz[n] = gzr; gz[g.NLP + n] = gzi;
                 lp += lpn;
-                sR += gzr; sL += gzi * er.wn[s]; sH += h_re + h_im; sHz2 += h_re * zr * zr + h_im * zi * zi;
+                sR += gzr; sL += gzi * er.wn[s]; sH += h_re + h_im; sHz2 += h_re * zr * zr + h_im * zi * zi;      // (the text of lik_sums)
                 sHzr2 += (h_re + h_im) * zr * zr; sHzi2 += (h_re + h_im) * zi * zi;
             }
         }
@@ -760,14 +752,14 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
         double gsc = 0.0;
         if (lane < 6) {
             const double t = lane == 0 ? T[0] : lane == 1 ? T[1] : lane == 2 ? T[2] : lane == 3 ? T[3] : lane == 4 ? T[4] : T[5];
-            double dl;
+            double dl;                                         // (the text of scalar_grad, bdrt_model_terms.h: as a call it costs registers here)
             if (lane == 0) dl = 100.0 * t;
             else if (lane == 1) dl = P.induc_scale * t;
             else dl = 0.05 * 2.0 * (0.05 * sraw) * t;
             gsc = sraw * (dl - sraw) + jac;
         } else if (lane < 9) {
             const double svs = lane == 6 ? S0 : lane == 7 ? S1 : S2;
-            gsc = -0.5 * sraw * svs - 6.0 + 5.0 * lean_rcp(sraw) + jac;
+            gsc = strength_grad(sraw, svs, jac);
         }
         gr[2 * KS] = gsc;
     }
@@ -790,7 +782,7 @@ __device__ __forceinline__ double wave_eval(const DevProblem &P, const WaveGeom 
 
 // ---- several distributions ------------------------------------------------------------------------------------------------------------
 // NB blocks of one basis length (series or parallel, each with its own generator table, band coefficients, sign constraint and scale),
-// the x_sum prior of the mixed models, the outlier error models: the formulas of bdrt_tile_hw.h / bdrt_solo_wide.h on the lane mapping of
+// the x_sum prior of the mixed models, the outlier error models: the model terms of bdrt_model_terms.h, as in bdrt_solo_wide.h, on the lane mapping of
 // wave_eval.  Slots of a lane: per block KS x-slots and KS ups-slots, then the scalars (lanes 0..5 the global ones, lane 6 + 3 b + i the
 // penalty strength d_i of block b), then the outlier parameters.  One wave per SIMD (512 registers).
 template <int KS, int NS, bool OM, int NB> constexpr int wave_slots_nb() { return 2 * KS * NB + 1 + (OM ? 2 * NS : 0); }
@@ -828,7 +820,7 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
     // ---- scalars --------------------------------------------------------------------------------------------------------------
     const double st = th[SC];
     const double sraw = lean_exp(st);
-    lp += lane < 6 + 3 * NB ? (lane < 6 ? -0.5 * sraw * sraw : -6.0 * st - 5.0 * lean_rcp(sraw)) + jac * st : 0.0;
+    lp += lane < 6 + 3 * NB ? (lane < 6 ? raw_prior_lp(sraw) : strength_prior_lp(sraw, st)) + jac * st : 0.0;
     double sc[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) sc[i] = wv_bcast(sraw, i);
@@ -927,7 +919,7 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
                 const double iu = lean_rcp(uk), iu2 = iu * iu;
                 const double q2 = d0 * v0[u] * v0[u] + d1 * v1[u] * v1[u] + d2 * v2[u] * v2[u];
                 const double ir = 0.15 * iu;
-                double lpk = -(tu + LOG_015) - 0.5 * q2 * iu2 - (P.ups_alpha + 1.0) * tu - P.ups_beta * ir + jac * tu;
+                double lpk = -(tu + LOG_015) - 0.5 * q2 * iu2 - (P.ups_alpha + 1.0) * tu - P.ups_beta * ir + jac * tu;      // (as wave_eval: the terms of ups_prior_k)
                 double gu = -iu + q2 * iu2 * iu;
                 if (k >= 1 && k + 1 < K) {
                     const double du = 0.5 * (uk - 0.5 * (um1 + up1)) * iu;
@@ -1005,62 +997,35 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
     double T[7], gzr_[NS], gzi_[NS];
     {
         double sR = 0, sL = 0, sH = 0, sHz2 = 0, sHzr2 = 0, sHzi2 = 0;
-        const double Rinf = 100.0 * sc[0], induc = sc[1] * P.induc_scale;
-        const double s_res = 0.05 * sc[2], a_p = 0.05 * sc[3], a_r = 0.05 * sc[4], a_i = 0.05 * sc[5];
-        const double c0 = P.sigma_min * P.sigma_min + s_res * s_res;
-        const double ap2 = a_p * a_p, ar2 = a_r * a_r, ai2 = a_i * a_i;
+        const LikConsts lc = lik_consts(P, sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int n = lane + 64 * s;
             const bool nv = n < nf;
-            double zr = Rinf, zi = induc * er.wn[s];
+            double zr = lc.Rinf, zi = lc.induc * er.wn[s];
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 if (!P.blk[b].is_parallel) { zr += yr[b][s]; zi += yi[b][s]; }
-                else {
-                    const double idn = lean_rcp(yr[b][s] * yr[b][s] + yi[b][s] * yi[b][s]);
-                    zr += yr[b][s] * idn;                   // Z_hat_p = conj(Y) / |Y|^2 (Parallel_modelcode.txt:47)
-                    zi += -yi[b][s] * idn;
-                }
+                else parallel_fwd(yr[b][s], yi[b][s], zr, zi);
             }
-            const double common = ar2 * zr * zr + ai2 * zi * zi;
-            [[maybe_unused]] double so_re = 0.0, so_im = 0.0, r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
+            [[maybe_unused]] OutlierSigma so = {0.0, 0.0};
+            [[maybe_unused]] double r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
             if constexpr (OM) {
                 t0 = th[SO + s]; t1 = th[SO + NS + s];
                 r0 = lean_exp(t0); r1 = lean_exp(t1);
-                if (P.outlier_mode == 1) so_re = so_im = 0.05 * r0 * r1;
-                else { so_re = 0.05 * r0; so_im = 0.05 * r1; }
+                so = outlier_sigma(P.outlier_mode, r0, r1);
             }
-            double s2_re = c0 + ap2 * zr * zr + common, s2_im = c0 + ap2 * zi * zi + common;
-            if constexpr (OM) { s2_re += so_re * so_re; s2_im += so_im * so_im; }
-            const double e_re = er.zre[s] - zr, e_im = er.zim[s] - zi;
-            const double prod = s2_re * s2_im, ip = lean_rcp(prod);
-            const double w_re = s2_im * ip, w_im = s2_re * ip;
-            const double lpn = -0.5 * lean_log(prod) - 0.5 * e_re * e_re * w_re - 0.5 * e_im * e_im * w_im;
-            const double h_re = -0.5 * w_re + 0.5 * e_re * e_re * w_re * w_re;
-            const double h_im = -0.5 * w_im + 0.5 * e_im * e_im * w_im * w_im;
-            const double gzr = e_re * w_re + 2.0 * zr * (h_re * (ap2 + ar2) + h_im * ar2);
-            const double gzi = e_im * w_im + 2.0 * zi * (h_im * (ap2 + ai2) + h_re * ai2);
-            gzr_[s] = nv ? gzr : 0.0; gzi_[s] = nv ? gzi : 0.0;
+            const LikPoint pt = lik_point<OM>(lc, zr, zi, er.zre[s], er.zim[s], so.re, so.im);
+            gzr_[s] = nv ? pt.gzr : 0.0; gzi_[s] = nv ? pt.gzi : 0.0;
             if constexpr (OM) {
-                double g0 = 0.0, g1 = 0.0, lpo = 0.0;
-                if (P.outlier_mode == 1) {
-                    const double dso = 2.0 * so_re * (h_re + h_im), ir1 = lean_rcp(r1);
-                    g0 = r0 * (0.05 * r1 * dso - P.so_lambda) + jac;
-                    g1 = 0.05 * r0 * r1 * dso - (P.so_alpha + 1.0) + P.so_beta * ir1 + jac;
-                    lpo = -P.so_lambda * r0 - (P.so_alpha + 1.0) * t1 - P.so_beta * ir1 + jac * (t0 + t1);
-                } else {
-                    g0 = r0 * (0.05 * 2.0 * so_re * h_re - P.so_lambda) + jac;
-                    g1 = r1 * (0.05 * 2.0 * so_im * h_im - P.so_lambda) + jac;
-                    lpo = -P.so_lambda * (r0 + r1) + jac * (t0 + t1);
-                }
-                gr[SO + s] = nv ? g0 : 0.0; gr[SO + NS + s] = nv ? g1 : 0.0;
-                lp += nv ? lpo : 0.0;
+                const OutlierTerms ot = outlier_terms(P, P.outlier_mode, jac, t0, t1, r0, r1, so, pt);
+                gr[SO + s] = nv ? ot.g0 : 0.0; gr[SO + NS + s] = nv ? ot.g1 : 0.0;
+                lp += nv ? ot.lp : 0.0;
             }
             if (nv) {
-                lp += lpn;
-                sR += gzr; sL += gzi * er.wn[s]; sH += h_re + h_im; sHz2 += h_re * zr * zr + h_im * zi * zi;
-                sHzr2 += (h_re + h_im) * zr * zr; sHzi2 += (h_re + h_im) * zi * zi;
+                lp += pt.lp;
+                const LikSums ls = lik_sums(pt, zr, zi, er.wn[s]);
+                sR += ls.R; sL += ls.L; sH += ls.H; sHz2 += ls.Hz2; sHzr2 += ls.Hzr2; sHzi2 += ls.Hzi2;
             }
         }
         const double q[8] = {sR, sL, sH, sHz2, sHzr2, sHzi2, lp, 0.0};
@@ -1081,13 +1046,7 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
         for (int s = 0; s < NS; ++s) {
             const int n = lane + 64 * s;
             double rr = gzr_[s], ri = gzi_[s];
-            if (B.is_parallel) {
-                const double a = yr[b][s], c = yi[b][s];
-                const double dn = a * a + c * c, id2 = lean_rcp(dn * dn);
-                const double dd = (c * c - a * a) * id2, doff = 2.0 * a * c * id2;
-                rr = gzr_[s] * dd + gzi_[s] * doff;
-                ri = -gzr_[s] * doff + gzi_[s] * dd;
-            }
+            if (B.is_parallel) parallel_bwd(yr[b][s], yi[b][s], rr, ri);
             if (n < nf) { gz[n] = rr * B.x_scale; gz[g.NLP + n] = ri * B.x_scale; }
         }
         wv_sync();
@@ -1117,7 +1076,7 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
         double gsc = 0.0;
         if (lane < 6) {
             const double t = lane == 0 ? T[0] : lane == 1 ? T[1] : lane == 2 ? T[2] : lane == 3 ? T[3] : lane == 4 ? T[4] : T[5];
-            double dl;
+            double dl;                                         // (the text of scalar_grad, bdrt_model_terms.h: as a call it costs registers here)
             if (lane == 0) dl = 100.0 * t;
             else if (lane == 1) dl = P.induc_scale * t;
             else dl = 0.05 * 2.0 * (0.05 * sraw) * t;
@@ -1128,7 +1087,7 @@ __device__ __forceinline__ double wave_eval_nb(const DevProblem &P, const WaveGe
             for (int b = 0; b < NB; ++b)
 #pragma unroll
                 for (int i = 0; i < 3; ++i) svs = lane == 6 + 3 * b + i ? Ssum[b][i] : svs;
-            gsc = -0.5 * sraw * svs - 6.0 + 5.0 * lean_rcp(sraw) + jac;
+            gsc = strength_grad(sraw, svs, jac);
         }
         gr[SC] = gsc;
     }
