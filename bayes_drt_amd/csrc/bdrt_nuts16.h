@@ -315,7 +315,12 @@ __global__ __launch_bounds__(NT) void nuts_kernel(const DevProblem *__restrict__
             auto early_state = [&]() { if constexpr (EARLY) load_state(); };
             // (D = 2 K + 9 here: K <= 59 / 91 / 107 for 4 / 6 / 7 elements per lane)
             constexpr int KU = NJ <= 4 ? 2 : (NJ <= 6 ? 3 : (NJ <= 7 ? 4 : 6));
-            logp_grad_tile_s1<true, 32, decltype(early_state), decltype(read_flags), TA, KU>(P, io, smem, early_state, read_flags);
+            // The evaluator reads the rows k = l32 + 32 u, u < KU, of theta_x and theta_ups without a clamp of k to K: from a
+            // parameter's offset o (o + K <= D <= 32 NJ) it walks less than 32 KU doubles past the chain's theta row -- for the
+            // workgroup's last chain into the cells behind the theta rows (lp, hand-over cells, ..., the uniforms: see the carve-up).
+            static_assert(32 * KU <= 3 * NC + 16 * NC, "unclamped parameter reads of the last chain end inside the workgroup's LDS");
+            // (K >= s1_kmin(NJ): the launcher picks MODE 2 only then, bdrt_sampler.hip::plan_tile16)
+            logp_grad_tile_s1<true, 32, decltype(early_state), decltype(read_flags), TA, KU, s1_kmin(NJ)>(P, io, smem, early_state, read_flags);
             if constexpr (!EARLY) load_state();
         }
         else if (MODE == 3) { logp_grad_tile_s1<false, 32, NoHook, NoHook, 0, KUX>(P, io, smem); load_state(); }

@@ -95,7 +95,9 @@ static void plan_tile16(SamplerPlan &pl, const DevProblem &P, const SamplerEnv &
     // the fast S1 kernel (theta rows resident in LDS, MODE 2) when the problem takes that path and the rows fit; else the S1 evaluator with
     // the sampler state in HBM (MODE 3: outlier parameters, K near 192); the general half-wave evaluator (MODE 4: several distributions,
     // parallel blocks); else the generic tile (MODE 1 Toeplitz operands / MODE 0)
-    const bool use_s1 = P.fast_s1 && P.outlier_mode == 0 && P.D <= 2 * RW && P.D <= 32 * 16 && nuts_lds_bytes(P, true) <= LDS_BUDGET;
+    // (K >= s1_kmin: what the MODE 2 instantiation takes for granted about its basis; it holds whenever D = 2 K + 9, the family's layout)
+    const bool use_s1 = P.fast_s1 && P.outlier_mode == 0 && P.D <= 2 * RW && P.D <= 32 * 16 && nuts_lds_bytes(P, true) <= LDS_BUDGET &&
+                        P.blk[0].K >= s1_kmin(s1_nj(P.D));
     const bool s1_hbm = !use_s1 && P.fast_s1 && P.D <= 32 * 16;
     const bool hw = P.fast_hw && P.D <= 32 * 27;
     pl.lds_bytes = !(s1_hbm || hw) ? nuts_lds_bytes(P, use_s1)

@@ -160,6 +160,13 @@ constexpr int WIN = UK + NTAP - 1;        // 22 values feed the 17-tap convoluti
 // parameters: s1_ku(K) <= the KU that goes with s1_nj(D), bdrt_nuts.hip)
 __host__ __device__ inline int s1_ku(int K) { return K <= 64 ? 2 : (K <= 96 ? 3 : (K <= 128 ? 4 : 6)); }
 __host__ __device__ inline int s1_nj(int D) { return D <= 32 * 4 ? 4 : (D <= 32 * 6 ? 6 : (D <= 32 * 7 ? 7 : (D <= 32 * 11 ? 11 : 16))); }
+// the shortest basis that the sampler's instantiation with NJ elements per lane serves: s1_nj picks NJ for 32 NJ' < D = 2 K + 9 <= 32 NJ
+// (NJ' the next smaller instantiation), so K >= 16 NJ' - 4 (rounded up).  The evaluator's range tests of the rows k < s1_kmin(NJ)
+// are compile-time facts (KMIN of logp_grad_tile_s1).
+__host__ __device__ constexpr int s1_kmin(int NJ) { return NJ == 6 ? 60 : (NJ == 7 ? 92 : (NJ == 11 ? 108 : (NJ == 16 ? 172 : 0))); }
+static_assert(2 * s1_kmin(6) + 9 > 32 * 4 && 2 * s1_kmin(7) + 9 > 32 * 6 && 2 * s1_kmin(11) + 9 > 32 * 7 && 2 * s1_kmin(16) + 9 > 32 * 11 &&
+              2 * (s1_kmin(6) - 1) + 9 <= 32 * 4 && 2 * (s1_kmin(7) - 1) + 9 <= 32 * 6 && 2 * (s1_kmin(11) - 1) + 9 <= 32 * 7 &&
+              2 * (s1_kmin(16) - 1) + 9 <= 32 * 11, "s1_kmin: the first K whose D = 2 K + 9 passes the next smaller instantiation of s1_nj");
 __host__ __device__ inline int s1_zrows(const DevProblem &P) { return P.toepA == 2 ? P.zrows : 16 * P.blk[0].tilesA; }
 template <int TA> __device__ __forceinline__ constexpr int toep_pad() { return TA == 2 ? 16 : 8; }
 template <int TA> __device__ __forceinline__ int toep_im_row(int nf) { return TA == 2 ? (nf + 3) & ~3 : nf; }
@@ -756,7 +763,22 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // TA: DevProblem::toepA (0, 1: toep_gemm, 2: toep_gemm_gen) -- the caller has run s1_toep_init once in this kernel.
 // KU: basis functions per lane of a half-wave, K <= 32 KU (2, 3, 4 or 6): every per-lane loop over k is unrolled KU (LPC = 64: KU / 2)
 // times whatever K is, so a short basis pays for a long one unless the caller picks the instantiation by K (s1_ku)
-template <bool LDSIO, int LPC = 32, class Hook = NoHook, class Hook1 = NoHook, int TA = 0, int KU = 6>
+// KMIN: a lower bound of K that the caller vouches for (s1_kmin; 0: none): the range tests of the rows that lie below it in every lane
+// are compile-time facts
+#ifndef BDRT_P1_LANE_BASE
+#define BDRT_P1_LANE_BASE 1              // LDSIO: P1's parameter reads at one lane base per row + immediate offsets (0: per-element addresses, clamped)
+#endif
+#ifndef BDRT_P1_STATIC_PRED
+#define BDRT_P1_STATIC_PRED 1            // P1's range tests k < K, k < KP of the rows below KMIN: none (0: a compare and selects per row)
+#endif
+#ifndef BDRT_P1_STORE_BASE
+#define BDRT_P1_STORE_BASE 0             // P1's stores to the operand tile and the private rows: one base per array + immediate offsets.  Measured
+                                         // and left off: 10 instructions fewer, 3 VGPRs fewer, and 0.2 % slower in 11 of 12 pairs (profiles/r09)
+#endif
+#ifndef BDRT_P3_LANE_BASE
+#define BDRT_P3_LANE_BASE 1              // P3's reads and stores of A x / g and of the table's odd-row taps: lane bases + immediate offsets, no clamp
+#endif
+template <bool LDSIO, int LPC = 32, class Hook = NoHook, class Hook1 = NoHook, int TA = 0, int KU = 6, int KMIN = 0>
 __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, double *smem, Hook before_backward = Hook(),
                                          Hook1 after_x_ready = Hook1())
 {
@@ -820,19 +842,36 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
     double lp = 0.0;
     int lp_lane = -1;                                      // the lane that ends up with the chain's total (-1: not summed yet)
     double x_[UKV];
+    // The rows k = l32 + LPC u of the phase, as of P3 and of the epilogue, differ by a constant from u to u + 1 in every array: swz's
+    // XOR term depends on k & 15 = l32 & 15 only.  One lane base per array and immediate offsets, formed from a copy of l32 that is
+    // opaque here (worked out of the round's l32 the bases are shared with later phases and stay live across the GEMMs).
+    static_assert(LPC % 16 == 0, "rows l32 + LPC u: the same swizzle");
+    // the u whose k lies below K (and below KP >= K) whatever the lane: KMIN <= K is the caller's promise (0: none)
+    auto below_kmin = [](int u) constexpr { return LPC * u + LPC - 1 < (BDRT_P1_STATIC_PRED ? KMIN : 0); };
     {
         double tx_[UKV], tu_[UKV];
-        // (loads first, unconditionally, from a clamped index; THEN the selects: a load under `k < K` becomes a branch around an
-        // LDS read with its own s_waitcnt -- six serial LDS round trips per phase, tools/isa_blocks.py)
+        int l1 = l32;
+        if constexpr (BDRT_P1_LANE_BASE || BDRT_P1_STORE_BASE) __asm__ volatile("" : "+v"(l1));
+        if constexpr (LDSIO && BDRT_P1_LANE_BASE) {
+            // The sampler's theta rows (LDS): no clamp of k to K.  What is read beyond K is dropped by the selects below; the walk
+            // ends less than LPC UKV doubles behind the row of the workgroup's last chain, inside what the sampler keeps behind its
+            // theta rows (bdrt_nuts16.h asserts that where it picks this instantiation).
+            const lds_cptr tx0 = (lds_cptr)th + (B.o_x + l1), tu0 = (lds_cptr)th + (B.o_ups + l1);
 #pragma unroll
-        for (int u = 0; u < UKV; ++u) {
-            const int k = l32 + LPC * u, kk = k < K ? k : 0;
-            tx_[u] = TH(B.o_x + kk);
-            tu_[u] = TH(B.o_ups + kk);
+            for (int u = 0; u < UKV; ++u) { tx_[u] = tx0[LPC * u]; tu_[u] = tu0[LPC * u]; }
+        } else {
+            // (loads first, unconditionally, from a clamped index; THEN the selects: a load under `k < K` becomes a branch around an
+            // LDS read with its own s_waitcnt -- six serial LDS round trips per phase, tools/isa_blocks.py)
+#pragma unroll
+            for (int u = 0; u < UKV; ++u) {
+                const int k = l32 + LPC * u, kk = k < K ? k : 0;
+                tx_[u] = TH(B.o_x + kk);
+                tu_[u] = TH(B.o_ups + kk);
+            }
         }
 #pragma unroll
         for (int u = 0; u < UKV; ++u) {
-            const bool in = l32 + LPC * u < K;
+            const bool in = below_kmin(u) || l32 + LPC * u < K;
             tx_[u] = in ? tx_[u] : 0.0;
             tu_[u] = in ? tu_[u] : 0.0;
         }
@@ -841,23 +880,36 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
         double ex_[UKV];
 #pragma unroll
         for (int u = 0; u < UKV; ++u) ex_[u] = lean_exp(tx_[u]);
+        // BDRT_P1_STORE_BASE: one base per array, rows and halo at immediate offsets (0: per-row addresses; the bases are dead code then)
+        [[maybe_unused]] double *const xs0 = Xs + swz(l1, c), *const xr0 = xrow + l1, *const wr0 = wrow + l1;
 #pragma unroll
         for (int u = 0; u < UKV; ++u) {
             const int k = l32 + LPC * u;
             double xr = 0.0;
-            if (k < K) {
+            if (below_kmin(u) || k < K) {
                 xr = B.is_pos ? ex_[u] : tx_[u];
                 if (B.is_pos) lp += jac * tx_[u];
                 PW(B.o_x + k, xr);
             }
             x_[u] = xr;
-            if (k < KP) Xs[swz(k, c)] = xr;
-            xrow[MAXBW + k] = xr;                          // zero beyond K: the convolution halo
-            wrow[MAXBW + k] = tu_[u];                      // theta_ups on its way to mapping M2
+            if constexpr (BDRT_P1_STORE_BASE) {
+                if (below_kmin(u) || k < KP) xs0[LPC * NC * u] = xr;
+                xr0[MAXBW + LPC * u] = xr;                 // zero beyond K: the convolution halo
+                wr0[MAXBW + LPC * u] = tu_[u];             // theta_ups on its way to mapping M2
+            } else {
+                if (k < KP) Xs[swz(k, c)] = xr;
+                xrow[MAXBW + k] = xr;
+                wrow[MAXBW + k] = tu_[u];
+            }
         }
         if (l32 < MAXBW) {
-            xrow[l32] = 0.0; xrow[MAXBW + LPC * UKV + l32] = 0.0;
-            wrow[l32] = 0.0; wrow[MAXBW + LPC * UKV + l32] = 0.0;
+            if constexpr (BDRT_P1_STORE_BASE) {
+                xr0[0] = 0.0; xr0[MAXBW + LPC * UKV] = 0.0;
+                wr0[0] = 0.0; wr0[MAXBW + LPC * UKV] = 0.0;
+            } else {
+                xrow[l32] = 0.0; xrow[MAXBW + LPC * UKV + l32] = 0.0;
+                wrow[l32] = 0.0; wrow[MAXBW + LPC * UKV + l32] = 0.0;
+            }
         }
     }
     static_assert(!TA || LPC == 32, "the Toeplitz-A GEMMs are written for 512 threads");
@@ -1097,16 +1149,41 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
         double lk0 = 0.0, lk1 = 0.0;
         if (TA == 2) toep_zero_split_gen<false>(nf, K, Xs, tid); else if (TA) toep_zero_split<false>(nf, K, Xs, tid);
         double pp_lo = 1.0, pp_hi = 1.0;
-        // (the phase's LDS reads in one batch, from a clamped row: under `n < nf` each of them is a round trip of its own)
+        // (the phase's LDS reads in one batch, whatever n is: under `n < nf` each of them is a round trip of its own)
         double azr_[UNV], azi_[UNV], tk0r_[UNV], tk0i_[UNV], tk1r_[UNV], tk1i_[UNV];
+        // The rows n = l32 + LPC v: one base for the real rows of Zh, one for the imaginary rows (nfi + n: another XOR term, the same
+        // for every v), one per part of the generator table; the rows at immediate offsets, read without a clamp of n to nf.  What
+        // is read beyond nf is never used (`n >= nf` below), and it is read from the workgroup's own LDS: the rows up to
+        // nfi + LPC UNV - 1 < 2 LPC UNV of Zh end inside the private rows behind it (2 RW rows of NC), the table positions up to
+        // tlen + TPAD + LPC UNV + 1 inside the table or the lane table / step lists behind it (bdrt_problem_create: nf, K >= 80 and
+        // tlen >= 176 with the lane table, nf, K >= 32 and tlen >= 2 TPAD + 63 with the step lists).
+        static_assert(LPC * UNV == 128 && 2 * LPC * UNV <= 2 * RW, "rows of Zh beyond nf: inside the chains' private rows");
+        static_assert(TA != 1 || LPC * UNV + 8 + 2 <= 176 + TOEP_LANE_DOUBLES, "table positions beyond nf: inside the lane table");
+        static_assert(TA != 2 || LPC * UNV + 16 + 2 <= 2 * 16 + 63 + TOEP_STEP_WORDS / 2, "table positions beyond nf: inside the step lists");
+        int l3 = l32;
+        if constexpr (BDRT_P3_LANE_BASE) __asm__ volatile("" : "+v"(l3));
+        double *const zr0 = Zh + swz(l3, c), *const zi0 = Zh + swz(nfi + l3, c);
+        if constexpr (BDRT_P3_LANE_BASE) {
+            const double *const t0 = TA ? Tt + (TPAD + l3 + rk - 1) : nullptr, *const t1 = TA ? t0 + tlen : nullptr;
 #pragma unroll
-        for (int v = 0; v < UNV; ++v) {
-            const int n = l32 + LPC * v, nn = n < nf ? n : 0;
-            azr_[v] = Zh[swz(nn, c)]; azi_[v] = Zh[swz(nfi + nn, c)];
-            tk0r_[v] = 0.0; tk0i_[v] = 0.0; tk1r_[v] = 0.0; tk1i_[v] = 0.0;
-            if (TA && rk > 0) {
-                tk0r_[v] = Tt[TPAD + nn + rk - 1]; tk0i_[v] = Tt[tlen + TPAD + nn + rk - 1];
-                if (rk > 1) { tk1r_[v] = Tt[TPAD + nn + rk - 2]; tk1i_[v] = Tt[tlen + TPAD + nn + rk - 2]; }
+            for (int v = 0; v < UNV; ++v) {
+                azr_[v] = zr0[LPC * NC * v]; azi_[v] = zi0[LPC * NC * v];
+                tk0r_[v] = 0.0; tk0i_[v] = 0.0; tk1r_[v] = 0.0; tk1i_[v] = 0.0;
+                if (TA && rk > 0) {
+                    tk0r_[v] = t0[LPC * v]; tk0i_[v] = t1[LPC * v];
+                    if (rk > 1) { tk1r_[v] = t0[LPC * v - 1]; tk1i_[v] = t1[LPC * v - 1]; }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < UNV; ++v) {
+                const int n = l32 + LPC * v, nn = n < nf ? n : 0;
+                azr_[v] = Zh[swz(nn, c)]; azi_[v] = Zh[swz(nfi + nn, c)];
+                tk0r_[v] = 0.0; tk0i_[v] = 0.0; tk1r_[v] = 0.0; tk1i_[v] = 0.0;
+                if (TA && rk > 0) {
+                    tk0r_[v] = Tt[TPAD + nn + rk - 1]; tk0i_[v] = Tt[tlen + TPAD + nn + rk - 1];
+                    if (rk > 1) { tk1r_[v] = Tt[TPAD + nn + rk - 2]; tk1i_[v] = Tt[tlen + TPAD + nn + rk - 2]; }
+                }
             }
         }
 #pragma unroll
@@ -1139,8 +1216,8 @@ __device__ inline void logp_grad_tile_s1(const DevProblem &P, const TileIO &io, 
             const double h_im = -0.5 * w_im + 0.5 * e_im * e_im * w_im * w_im;
             const double gzr = e_re * w_re + 2.0 * zr * (h_re * (ap2 + ar2) + h_im * ar2);
             const double gzi = e_im * w_im + 2.0 * zi * (h_im * (ap2 + ai2) + h_re * ai2);
-            Zh[swz(n, c)] = gzr;
-            Zh[swz(nfi + n, c)] = gzi;
+            if constexpr (BDRT_P3_LANE_BASE) { zr0[LPC * NC * v] = gzr; zi0[LPC * NC * v] = gzi; }
+            else { Zh[swz(n, c)] = gzr; Zh[swz(nfi + n, c)] = gzi; }
             if (TA && rk > 0) {            // A_part[n][K - rk + j] = tg[part][n + rk - 1 - j]
                 lk0 = fma(tk0r_[v], gzr, fma(tk0i_[v], gzi, lk0));
                 if (rk > 1) lk1 = fma(tk1r_[v], gzr, fma(tk1i_[v], gzi, lk1));
