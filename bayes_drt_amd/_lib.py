@@ -62,6 +62,20 @@ class ChainDiag(C.Structure):
                 ('stepsize', C.c_double), ('mean_accept', C.c_double)]
 
 
+class NewtonSolveRecord(C.Structure):
+    """bdrt_newton_solve_record: what one launch of the Newton iteration's damped solve committed (bdrt_debug_newton_solve)"""
+    _fields_ = [('ok', C.c_int), ('attempt', C.c_int), ('rc', C.c_int), ('done', C.c_int),
+                ('lam', C.c_double), ('pred', C.c_double), ('gs', C.c_double), ('ss', C.c_double)]
+
+
+class NewtonState(C.Structure):
+    """bdrt_newton_state: the Newton iteration's per-fit state before and after the verdict (bdrt_debug_newton_accept)"""
+    _fields_ = [('lp', C.c_double), ('lam', C.c_double), ('pred', C.c_double), ('gs', C.c_double), ('ss', C.c_double),
+                ('grad_inf', C.c_double), ('tol', C.c_double), ('lp_trial', C.c_double),
+                ('iters', C.c_int), ('max_iter', C.c_int), ('lin', C.c_int), ('rc', C.c_int), ('done', C.c_int),
+                ('need_hess', C.c_int), ('n_evals', C.c_int), ('pad', C.c_int)]
+
+
 # every symbol include/bdrt.h declares (tests/test_abi.py checks the library exports each of them)
 SYMBOLS = [
     'bdrt_build_A', 'bdrt_build_A_basis', 'bdrt_build_L', 'bdrt_build_L_rect', 'bdrt_build_M',
@@ -79,6 +93,7 @@ SYMBOLS = [
     'bdrt_pointwise_loglik', 'bdrt_psis_loo', 'bdrt_psis_loo_max_draws', 'bdrt_psis_predict', 'bdrt_psis_predict_max_draws',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
+    'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept',
 ]
 
 
@@ -190,6 +205,9 @@ def load_library():
     lib.bdrt_rank_max_draws.argtypes = []
     lib.bdrt_rank_max_draws.restype = C.c_int
     lib.bdrt_debug_rank_z.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    lib.bdrt_debug_newton_solve.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp,
+                                            C.POINTER(NewtonSolveRecord)]
+    lib.bdrt_debug_newton_accept.argtypes = [C.POINTER(NewtonState), vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int]
     lib.bdrt_pointwise_loglik.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.bdrt_psis_loo.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.bdrt_psis_loo_max_draws.argtypes = []

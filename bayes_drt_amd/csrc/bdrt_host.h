@@ -227,6 +227,12 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
 // scale (Series_pos only, else 1); held_out [D] (optional): the coefficients held at their floor
 int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double *H_out, double *held_out);
 
+// one launch of the damped solve / of the verdict on supplied data (tests; include/bdrt.h, debug section): no problem, the current device
+int newton_solve_at(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz, const double *held,
+                    double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out, bdrt_newton_solve_record *rec);
+int newton_accept_at(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t, const double *gt,
+                     const double *tz, const double *held, double floor_x, int o_x, int Kx);
+
 }  // namespace bdrt
 
 struct bdrt_problem {

@@ -188,4 +188,23 @@ int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H
     return bdrt_debug_hessian_lin(p, theta, spec, 0, H_out, nullptr);
 }
 
+// one launch of the Newton iteration's damped solve / of its verdict on the trial points, on the caller's data (tests)
+int bdrt_debug_newton_solve(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz,
+                            const double *held, double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out,
+                            bdrt_newton_solve_record *rec)
+{
+    if (!H || !g || !x || !L_out || !s_out || !trial_out || !rec || D < 1 || natt < 1 || natt > 6 || !(lam > 0.0) ||
+        (tz && (o_x < 0 || Kx < 0 || o_x + Kx > D))) { set_error("bdrt_debug_newton_solve: bad arguments"); return -1; }
+    return newton_solve_at(H, g, x, D, lam, natt, tz, held, floor_x, o_x, Kx, L_out, s_out, trial_out, rec);
+}
+
+int bdrt_debug_newton_accept(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t,
+                             const double *gt, const double *tz, const double *held, double floor_x, int o_x, int Kx)
+{
+    if (!st || !x || !g || !trial || !lp_t || !gt || D < 1 || (tz && (o_x < 0 || Kx < 0 || o_x + Kx > D))) {
+        set_error("bdrt_debug_newton_accept: bad arguments"); return -1;
+    }
+    return newton_accept_at(st, x, g, D, trial, lp_t, gt, tz, held, floor_x, o_x, Kx);
+}
+
 }  // extern "C"

@@ -670,6 +670,12 @@ __global__ __launch_bounds__(256) void newton_init_kernel(NewtonBufs b, int n_fi
     }
 }
 
+// dynamic LDS of newton_solve_kernel: right-hand side, reduction scratch, chol_blocked's diagonal block, pivots, panel and flag
+static size_t newton_solve_lds_bytes(int Dp)
+{
+    return ((size_t)Dp + 64 + 16 * 17 + 16 + (size_t)Dp * 17 + 2) * sizeof(double);
+}
+
 // Newton polish of n_fits points (x0 [n_fits][D] on the host); results back to x_out, reports filled
 int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
                          double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out)
@@ -751,7 +757,7 @@ int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fi
     int rc;
     if ((rc = launch_logp_grad(&P, b.x, d_spec1, n_fits, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
     hipLaunchKernelGGL(newton_init_kernel, dim3(n_fits), dim3(256), 0, st, b, n_fits, (const double *)d_lpt, (const double *)b.gt);
-    const size_t lds_solve = ((size_t)Dp + 64 + 16 * 17 + 16 + (size_t)Dp * 17 + 2) * sizeof(double);
+    const size_t lds_solve = newton_solve_lds_bytes(Dp);
     BDRT_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
     // The sequence of launches of one Levenberg-Marquardt round does not depend on what the round decides (kernels skip the
     // fits that are done; a fit that keeps its Hessian after a rejected trial skips the probe writes and ignores the probe
@@ -895,6 +901,106 @@ int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double 
     // (the kernels write the block lower triangle: mirror it)
     for (int i = 0; i < D; ++i)
         for (int j = 0; j <= i; ++j) H_out[(size_t)i * D + j] = H_out[(size_t)j * D + i] = hh[(size_t)i * Dp + j];
+    return 0;
+}
+
+// the debug entries' stand-in for the closed-form Hessian's workspace: the three fields the solve, gather and accept kernels read --
+// tz [D], act [D], the floor -- and the layout offsets that point at them (tz == nullptr: the log scale, no workspace)
+static int debug_lin_workspace(NewtonBufs &b, DevBuf<double> &hws, int D, const double *tz, const double *held, double floor_x, int o_x, int Kx)
+{
+    if (!tz) return 0;
+    std::vector<double> w((size_t)2 * D + 1);
+    for (int i = 0; i < D; ++i) { w[i] = tz[i]; w[(size_t)D + i] = held && held[i] != 0.0 ? 1.0 : 0.0; }
+    w[(size_t)2 * D] = floor_x;
+    if (int rc = upload(hws, w.data(), w.size())) return rc;
+    b.analytic = 1; b.lin_ok = 1; b.hws = hws;
+    b.hl_total = 2 * D + 1; b.hl_tz = 0; b.hl_act = D; b.hl_floor = 2 * D; b.o_x = o_x; b.Kx = Kx;
+    return 0;
+}
+
+// One launch of the damped solve on supplied data (tests): newton_build_kernel's need_hess == 0 branch, newton_solve_kernel with
+// natt attempts, newton_gather_kernel -- the launches of a round of newton_polish_device for one fit that keeps its Hessian.
+int newton_solve_at(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz, const double *held,
+                    double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out, bdrt_newton_solve_record *rec)
+{
+    const int Dp = (D + 15) & ~15;
+    const size_t lds_solve = newton_solve_lds_bytes(Dp), nM = (size_t)Dp * Dp;
+    if (lds_solve + 64 > 160 * 1024) { set_error("bdrt_debug_newton_solve: D = %d needs %zu bytes of LDS", D, lds_solve); return -2; }     // (+ the kernel's static LDS)
+    bind_process_device();
+    NewtonBufs b;
+    memset(&b, 0, sizeof(b));
+    b.D = D; b.Dp = Dp;
+    DevBuf<double> dx, dg, ds, dxt, dH, dM, dM2, hws, dtrial;
+    DevBuf<NewtonAttempt> datt;
+    DevBuf<NewtonState> dst;
+    DevBuf<int> d_act;
+    std::vector<double> hh(nM, 0.0);
+    for (int i = 0; i < D; ++i) memcpy(&hh[(size_t)i * Dp], H + (size_t)i * D, (size_t)D * sizeof(double));
+    NewtonState hs;
+    memset(&hs, 0, sizeof(hs));
+    hs.lam = lam; hs.rc = 1; hs.lin = tz ? 1 : 0;
+    const int zero = 0;
+    int rc;
+    if ((rc = upload(dx, x, (size_t)D)) || (rc = upload(dg, g, (size_t)D)) || (rc = upload(dH, hh.data(), nM)) || (rc = upload(dst, &hs, 1)) ||
+        (rc = upload(d_act, &zero, 1)) || (rc = debug_lin_workspace(b, hws, D, tz, held, floor_x, o_x, Kx))) return rc;
+    BDRT_HIP(ds.alloc((size_t)NW_ATT * D)); BDRT_HIP(dxt.alloc((size_t)NW_ATT * D)); BDRT_HIP(dtrial.alloc((size_t)NW_TRY * D));
+    BDRT_HIP(dM.alloc(nM)); BDRT_HIP(datt.alloc(NW_ATT));
+    BDRT_HIP(hipMemset(datt, 0, NW_ATT * sizeof(NewtonAttempt)));
+    if (natt > 1) {
+        // (the speculative attempts write the lower block triangle of their matrices only: the rest reads as zero)
+        BDRT_HIP(dM2.alloc((NW_ATT - 1) * nM));
+        BDRT_HIP(hipMemset(dM2, 0, (NW_ATT - 1) * nM * sizeof(double)));
+    }
+    b.x = dx; b.g = dg; b.s = ds; b.xt = dxt; b.H = dH; b.M = dM; b.M2 = dM2; b.att = datt; b.st = dst;
+    BDRT_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
+    hipStream_t st = nullptr;
+    hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, 1), dim3(256), 0, st, b, (const int *)d_act.p, 1);
+    hipLaunchKernelGGL(newton_solve_kernel, dim3(1, natt), dim3(NW_NT), lds_solve, st, b, (const int *)d_act.p, 1, natt);
+    hipLaunchKernelGGL(newton_gather_kernel, dim3(1, NW_TRY), dim3(128), 0, st, b, (const int *)d_act.p, 1, dtrial.p, natt);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipStreamSynchronize(st));
+    NewtonAttempt hatt[NW_ATT];
+    if (download(hatt, (const NewtonAttempt *)datt.p, (size_t)NW_ATT) || download(&hs, (const NewtonState *)dst.p, 1)) return -10;
+    int c = 0;
+    while (c + 1 < natt && !hatt[c].ok) ++c;                           // the gather kernel's choice
+    const double *Mc = c ? dM2.p + (size_t)(c - 1) * nM : dM.p;
+    if (download(L_out, Mc, nM) || download(s_out, (const double *)ds.p + (size_t)c * D, (size_t)D) ||
+        download(trial_out, (const double *)dtrial.p, (size_t)NW_TRY * D)) return -10;
+    rec->ok = hatt[c].ok; rec->attempt = c; rec->rc = hs.rc; rec->done = hs.done;
+    rec->lam = hs.lam; rec->pred = hs.pred; rec->gs = hs.gs; rec->ss = hs.ss;
+    return 0;
+}
+
+// One launch of newton_accept_kernel on supplied data (tests): the state, the point and its gradient before and after
+int newton_accept_at(bdrt_newton_state *s, double *x, double *g, int D, const double *trial, const double *lp_t, const double *gt,
+                     const double *tz, const double *held, double floor_x, int o_x, int Kx)
+{
+    bind_process_device();
+    NewtonBufs b;
+    memset(&b, 0, sizeof(b));
+    b.D = D; b.Dp = (D + 15) & ~15;
+    DevBuf<double> dx, dg, dgt, dtrial, dlp, hws;
+    DevBuf<NewtonState> dst;
+    DevBuf<int> d_act;
+    NewtonState hs;
+    memset(&hs, 0, sizeof(hs));
+    hs.lp = s->lp; hs.lam = s->lam; hs.pred = s->pred; hs.gs = s->gs; hs.ss = s->ss; hs.grad_inf = s->grad_inf; hs.tol = s->tol;
+    hs.lp_trial = s->lp_trial; hs.iters = s->iters; hs.max_iter = s->max_iter; hs.lin = tz ? s->lin : 0; hs.rc = s->rc; hs.done = s->done;
+    hs.need_hess = s->need_hess; hs.n_evals = s->n_evals;
+    const int zero = 0;
+    int rc;
+    if ((rc = upload(dx, (const double *)x, (size_t)D)) || (rc = upload(dg, (const double *)g, (size_t)D)) ||
+        (rc = upload(dgt, gt, (size_t)NW_TRY * D)) || (rc = upload(dtrial, trial, (size_t)NW_TRY * D)) || (rc = upload(dlp, lp_t, (size_t)NW_TRY)) ||
+        (rc = upload(dst, &hs, 1)) || (rc = upload(d_act, &zero, 1)) || (rc = debug_lin_workspace(b, hws, D, tz, held, floor_x, o_x, Kx))) return rc;
+    b.x = dx; b.g = dg; b.gt = dgt; b.st = dst;
+    hipStream_t st = nullptr;
+    hipLaunchKernelGGL(newton_accept_kernel, dim3(1), dim3(256), 0, st, b, (const int *)d_act.p, 1, (const double *)dlp.p, (const double *)dtrial.p);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipStreamSynchronize(st));
+    if (download(&hs, (const NewtonState *)dst.p, 1) || download(x, (const double *)dx.p, (size_t)D) || download(g, (const double *)dg.p, (size_t)D)) return -10;
+    s->lp = hs.lp; s->lam = hs.lam; s->pred = hs.pred; s->gs = hs.gs; s->ss = hs.ss; s->grad_inf = hs.grad_inf; s->tol = hs.tol;
+    s->lp_trial = hs.lp_trial; s->iters = hs.iters; s->max_iter = hs.max_iter; s->lin = hs.lin; s->rc = hs.rc; s->done = hs.done;
+    s->need_hess = hs.need_hess; s->n_evals = hs.n_evals;
     return 0;
 }
 

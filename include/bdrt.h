@@ -407,6 +407,35 @@ int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H
  * host's in the last bit). */
 int bdrt_debug_rank_z(const double *y, int M, int N, int is_pos, int what, double *z_out);
 
+/* One launch of the Newton iteration's damped solve on supplied data (no problem handle; the current device):
+ * newton_build_kernel (M = -H + lam I from H), newton_solve_kernel with `natt` attempts (1 .. 6) side by side,
+ * newton_gather_kernel.  H [D x D] symmetric, row-major; g, x [D].  The linear scale of the coefficients (slots o_x ..
+ * o_x + Kx - 1) when tz is not NULL: tz [D] = dy/dz per slot, held [D] != 0 for a coefficient held at its floor, floor_x the
+ * floor; NULL for the log scale (held, floor_x, o_x, Kx are ignored then).  Outputs, on the host: L_out [Dp x Dp], Dp = D
+ * rounded up to 16, the matrix of the committed attempt as the kernel leaves it (the factor in its lower triangle, the
+ * identity on the padding; what is above the diagonal is not part of the result); s_out [D]; trial_out [4][D], the points for
+ * the steps s, s/2, s/4, s/8.  Returns -2 without launching when D needs more LDS than a workgroup can have. */
+typedef struct {
+    int ok;                 /* the committed attempt factored and gave a finite step */
+    int attempt;            /* index of the committed attempt: the first that succeeded, the last one if none did */
+    int rc, done;           /* the fit's state after the gather kernel (rc 2, done 1: damping exhausted) */
+    double lam;             /* the damping of the committed attempt (beyond 1e12 when none factored) */
+    double pred, gs, ss;    /* predicted increase, g.s and s.s as the state holds them (valid when ok) */
+} bdrt_newton_solve_record;
+int bdrt_debug_newton_solve(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz,
+                            const double *held, double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out,
+                            bdrt_newton_solve_record *rec);
+/* One launch of newton_accept_kernel on supplied data: the verdict on the four trial points.  st: the fit's state before
+ * (lp, lam, pred, gs, ss, grad_inf, tol, iters, max_iter, lin are read; rc, done, need_hess, n_evals are taken as given) and
+ * after.  x, g [D]: in and out; trial [4][D], lp_t [4], gt [4][D]: the trial points, their log-posteriors and gradients.
+ * tz, held, floor_x, o_x, Kx as above (they matter when st->lin != 0; tz == NULL clears lin). */
+typedef struct {
+    double lp, lam, pred, gs, ss, grad_inf, tol, lp_trial;
+    int iters, max_iter, lin, rc, done, need_hess, n_evals, pad;
+} bdrt_newton_state;
+int bdrt_debug_newton_accept(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t,
+                             const double *gt, const double *tz, const double *held, double floor_x, int o_x, int Kx);
+
 #ifdef __cplusplus
 }
 #endif
