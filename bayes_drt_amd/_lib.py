@@ -91,6 +91,7 @@ SYMBOLS = [
     'bdrt_sampler_diagnostics', 'bdrt_diagnostics',
     'bdrt_rank_diagnostics', 'bdrt_sampler_rank_diagnostics', 'bdrt_rank_max_draws',
     'bdrt_pointwise_loglik', 'bdrt_psis_loo', 'bdrt_psis_loo_max_draws', 'bdrt_psis_predict', 'bdrt_psis_predict_max_draws',
+    'bdrt_sampler_loo', 'bdrt_sampler_loo_predict', 'bdrt_sampler_loo_group_bytes',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
     'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept',
@@ -215,6 +216,12 @@ def load_library():
     lib.bdrt_psis_predict.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp] + [vp] * 8
     lib.bdrt_psis_predict_max_draws.argtypes = []
     lib.bdrt_psis_predict_max_draws.restype = C.c_int
+    # (sampler, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, reff_mode, reff_in, chunk_bytes), then the outputs
+    loo_front = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
+    lib.bdrt_sampler_loo.argtypes = loo_front + [vp] * 6
+    lib.bdrt_sampler_loo_predict.argtypes = loo_front + [vp] * 9
+    lib.bdrt_sampler_loo_group_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.bdrt_sampler_loo_group_bytes.restype = C.c_size_t
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

@@ -214,6 +214,31 @@ int post_percentiles_device(const double *dX, int rows, int K, long ldx, const d
 int diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M, int N,
                         int C, double *mean, double *sd, double *n_eff, double *rhat, hipStream_t stream);
 
+// the same with the flags and the four outputs [G x C] on the DEVICE (dExp may be null); returns after the stream has finished
+int diagnostics_device(const double *dX, long unit_stride, long row_stride, const unsigned char *dExp, int G, int M, int N, int C,
+                       double *dMean, double *dSd, double *dNeff, double *dRhat, hipStream_t stream);
+
+// PSIS-LOO and the LOO predictive check of draws that are on the device (bdrt_sampler_loo, bdrt_sampler_loo_predict; bdrt_loo.hip,
+// bdrt_loo_predict.hip).  G groups of S = chains * n_draws consecutive rows (chain-major) of `draws`; per chunk of groups the batch
+// evaluator gives Z_hat and sigma_tot of the rows, and the kernels of the host-staged entry points reduce them against the data
+// row of the group's spectrum, scalar observations [col0, col0 + ncols) of the 2 Nf.  Outputs on the host, per group.
+constexpr size_t LOO_CHUNK_DEFAULT = (size_t)1 << 30;      // device bytes of one chunk's scratch when chunk_bytes == 0
+struct LooDraws {
+    Problem *prob;
+    const double *draws;            // device [G * S][D], unconstrained
+    const int *spec;                // host [G]: the spectrum the units of each group were sampled against
+    int G, chains, n_draws;
+    int pair, col0, ncols;          // pair: real and imaginary part of a frequency are one unit (the full range only)
+    int reff_mode;                  // 0: 1; 1: reff_in [G][units]; 2: n_eff / S of exp(ll - max ll) per unit
+    const double *reff_in;
+    size_t chunk_bytes;             // 0: LOO_CHUNK_DEFAULT
+    hipStream_t stream;             // idle when the call starts; every launch goes here
+};
+size_t loo_draws_group_bytes(const LooDraws &j, bool predict);       // what one group adds to a chunk's scratch
+int loo_of_draws(const LooDraws &j, double *lpd, double *elpd_loo, double *pareto_k, double *p_waic, int *n_tail, double *reff_out);
+int loo_predict_of_draws(const LooDraws &j, double *mean, double *sd, double *pit, double *mean_post, double *sd_post,
+                         double *pit_post, double *pareto_k, int *n_tail, double *reff_out);
+
 // rank-normalised diagnostics (bdrt_rank.hip) of the same layout of DEVICE draws, on the split chains; outputs [G x C] on the host
 int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M,
                              int N, int C, double p_lo, double p_hi, double *rhat, double *ess_bulk, double *ess_tail,

@@ -243,6 +243,58 @@ static size_t predict_lds_bytes(int S, int cap)
 static_assert(((size_t)LO_MAX_S + LP_RED + 4 * LO_MAX_M + 4) * 8 + (256 + 4 + (LO_MAX_S + 4) / 5) * 4 <= 160 * 1024,
               "predict_kernel: the column and the tail indices of LO_MAX_S draws must fit the LDS of a CU");
 
+int loo_predict_device(const double *dTm, const double *dTs, const double *dz, const int *dM, int G, int S, int N2, int pair,
+                       double *dOut, int *dNtail, hipStream_t stream)
+{
+    const int U = pair ? N2 / 2 : N2, cap = (S + 4) / 5;
+    const size_t units = (size_t)G * U, nsc = (size_t)G * N2, lds = predict_lds_bytes(S, cap);
+    static LdsAttrCache cache;
+    BDRT_HIP(cache.ensure(lds, [&]() {
+        return hipFuncSetAttribute((const void *)predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }));
+    PredictArgs a;
+    a.Tm = dTm; a.Ts = dTs; a.z = dz; a.M = dM;
+    a.S = S; a.cap = cap; a.N2 = N2; a.U = U; a.pair = pair;
+    a.c0 = -0.5 * std::log(2.0 * M_PI); a.log_dbl_min = std::log(DBL_MIN);
+    a.out = dOut; a.khat = dOut + 6 * nsc; a.ntail = dNtail;
+    hipLaunchKernelGGL(predict_kernel, dim3((unsigned)units), dim3(LO_NT), lds, stream, a);
+    BDRT_HIP(hipGetLastError());
+    return 0;
+}
+
+int loo_predict_of_draws(const LooDraws &j, double *mean, double *sd, double *pit, double *mean_post, double *sd_post,
+                         double *pit_post, double *pareto_k, int *n_tail, double *reff_out)
+{
+    const char *who = "bdrt_sampler_loo_predict";
+    const int S = j.chains * j.n_draws, U = j.pair ? j.ncols / 2 : j.ncols;
+    const size_t N2 = 2 * (size_t)j.prob->dev.nf;
+    std::vector<double> reff((size_t)j.G * U);
+    LooStage st;
+    DevBuf<double> Tm, Ts;
+    if (const int rc = st.alloc(j, true, 6 * (size_t)j.ncols + U)) return rc;
+    BDRT_HIP(Tm.alloc((size_t)st.gmax * S * j.ncols));
+    BDRT_HIP(Ts.alloc((size_t)st.gmax * S * j.ncols));
+    for (int g0 = 0; g0 < j.G; g0 += st.gmax) {
+        const int gn = std::min(st.gmax, j.G - g0);
+        const size_t units = (size_t)gn * U, nsc = (size_t)gn * j.ncols, o = (size_t)g0 * U, osc = (size_t)g0 * j.ncols;
+        if (nsc > 0x7fffffffull) { set_error("%s: too many observations", who); return -2; }
+        int rc;
+        if ((rc = st.eval(j, g0, gn)) || (j.reff_mode == 2 && (rc = st.loglik_T(who, j, gn))) ||
+            (rc = st.tails(who, j, g0, gn, reff.data() + o)) ||
+            (rc = loo_transpose_device(who, st.zh.p + j.col0, Tm, gn, S, j.ncols, N2, j.stream)) ||
+            (rc = loo_transpose_device(who, st.sg.p + j.col0, Ts, gn, S, j.ncols, N2, j.stream)) ||
+            (rc = loo_predict_device(Tm, Ts, st.z, st.M, gn, S, j.ncols, j.pair, st.out, st.ntail, j.stream)))
+            return rc;
+        BDRT_HIP(hipStreamSynchronize(j.stream));
+        double *const outs[6] = {mean + osc, sd + osc, pit + osc, mean_post + osc, sd_post + osc, pit_post + osc};
+        if (download_planes(st.out, nsc, outs, 6)) return -10;
+        BDRT_HIP(hipMemcpy(pareto_k + o, st.out.p + 6 * nsc, units * sizeof(double), hipMemcpyDeviceToHost));
+        BDRT_HIP(hipMemcpy(n_tail + o, st.ntail, units * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (reff_out) std::copy(reff.begin(), reff.end(), reff_out);
+    return 0;
+}
+
 }  // namespace bdrt
 
 using namespace bdrt;
@@ -267,8 +319,6 @@ int bdrt_psis_predict(const double *Zhat, const double *sig, const double *z, in
     std::vector<int> M;
     if (loo_tail_lengths("bdrt_psis_predict", S, units, reff, M)) return -1;
     bind_process_device();
-    const int cap = (S + 4) / 5;
-    const size_t lds = predict_lds_bytes(S, cap);
     DevBuf<double> dIn, dTm, dTs, dz, dOut;
     DevBuf<int> dM, dNtail;
     if (upload(dz, z, nsc) || upload(dM, M.data(), units)) return -10;
@@ -276,22 +326,12 @@ int bdrt_psis_predict(const double *Zhat, const double *sig, const double *z, in
     BDRT_HIP(dTs.alloc(nel));
     BDRT_HIP(dIn.alloc(nel));
     BDRT_HIP(hipMemcpy(dIn, Zhat, nel * sizeof(double), hipMemcpyHostToDevice));
-    if (const int rc = loo_transpose_device("bdrt_psis_predict", dIn, dTm, G, S, N2)) return rc;
+    if (const int rc = loo_transpose_device("bdrt_psis_predict", dIn, dTm, G, S, N2, (size_t)N2, nullptr)) return rc;
     BDRT_HIP(hipMemcpy(dIn, sig, nel * sizeof(double), hipMemcpyHostToDevice));      // (stream order: behind the first transpose)
-    if (const int rc = loo_transpose_device("bdrt_psis_predict", dIn, dTs, G, S, N2)) return rc;
+    if (const int rc = loo_transpose_device("bdrt_psis_predict", dIn, dTs, G, S, N2, (size_t)N2, nullptr)) return rc;
     BDRT_HIP(dOut.alloc(6 * nsc + units));
     BDRT_HIP(dNtail.alloc(units));
-    static LdsAttrCache cache;
-    BDRT_HIP(cache.ensure(lds, [&]() {
-        return hipFuncSetAttribute((const void *)predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }));
-    PredictArgs a;
-    a.Tm = dTm; a.Ts = dTs; a.z = dz; a.M = dM;
-    a.S = S; a.cap = cap; a.N2 = N2; a.U = U; a.pair = pair;
-    a.c0 = -0.5 * std::log(2.0 * M_PI); a.log_dbl_min = std::log(DBL_MIN);
-    a.out = dOut; a.khat = dOut + 6 * nsc; a.ntail = dNtail;
-    hipLaunchKernelGGL(predict_kernel, dim3((unsigned)units), dim3(LO_NT), lds, nullptr, a);
-    BDRT_HIP(hipGetLastError());
+    if (const int rc = loo_predict_device(dTm, dTs, dz, dM, G, S, N2, pair, dOut, dNtail, nullptr)) return rc;
     BDRT_HIP(hipDeviceSynchronize());
     double *const outs[6] = {mean, sd, pit, mean_post, sd_post, pit_post};
     if (download_planes(dOut, nsc, outs, 6)) return -10;

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <vector>
 
+#include "bdrt_host.h"
 #include "bdrt_stats.h"
 
 namespace bdrt {
@@ -21,8 +22,34 @@ constexpr int LO_TILE = 32;
 // tail length M = ceil(min(S / 5, 3 sqrt(S / reff))) per column, as the numpy statement computes it; -1 and the error text
 // (in the name of `who`) when a reff is not a positive number
 int loo_tail_lengths(const char *who, int S, size_t ncol, const double *reff, std::vector<int> &M);
-// device [G][S][N] -> device [G][N][S] (transpose_kernel); -2 when the grid would not fit, -10 on a launch error
-int loo_transpose_device(const char *who, const double *dIn, double *dT, int G, int S, int N);
+// The device-pointer cores of the entry points: each enqueues on `stream` and returns; the caller synchronises.
+// device [G][S][N] (rows of ld >= N doubles) -> device [G][N][S] (transpose_kernel); -2 when the grid would not fit, -10 on a
+// launch error
+int loo_transpose_device(const char *who, const double *dIn, double *dT, int G, int S, int N, size_t ld, hipStream_t stream);
+// loglik_kernel: dZh, dSg rows of ld doubles of which the N2 from the pointer on count, dz [G][N2] -> dLl [rows][N2 or N2 / 2]
+int loo_loglik_device(const double *dZh, const double *dSg, const double *dz, size_t rows, int S, int N2, size_t ld, int pair,
+                      double *dLl, hipStream_t stream);
+// psis_kernel on T [ncol][S] with tail lengths dM [ncol]: dOut 4 planes of ncol (lpd, elpd_loo, pareto_k, p_waic), dNtail [ncol]
+int loo_psis_device(const double *dT, const int *dM, size_t ncol, int S, double *dOut, int *dNtail, hipStream_t stream);
+// predict_kernel on the transposed Z_hat and sigma_tot [G][N2][S], dz [G][N2], dM [units]: dOut 6 planes of G N2 (mean, sd, pit,
+// mean_post, sd_post, pit_post), then pareto_k [units]; dNtail [units]
+int loo_predict_device(const double *dTm, const double *dTs, const double *dz, const int *dM, int G, int S, int N2, int pair,
+                       double *dOut, int *dNtail, hipStream_t stream);
+
+// Scratch of one chunk of groups of a LooDraws job (bdrt_host.h) and the steps its two reductions share (bdrt_loo.hip)
+struct LooStage {
+    DevBuf<double> par, zh, sg, lp;              // the evaluator's outputs for the chunk's rows
+    DevBuf<double> z;                            // [gmax][ncols] data rows
+    DevBuf<double> ll, T, lik, dg;               // ll, its transpose; reff_mode 2: the likelihood draws, diag_kernel's outputs
+    DevBuf<double> out;                          // result planes of the chunk
+    DevBuf<int> M, ntail;
+    std::vector<int> hM;
+    int gmax = 0;                                // groups per chunk
+    int alloc(const LooDraws &j, bool predict, size_t out_doubles_per_group);
+    int eval(const LooDraws &j, int g0, int gn);
+    int loglik_T(const char *who, const LooDraws &j, int gn);
+    int tails(const char *who, const LooDraws &j, int g0, int gn, double *reff);
+};
 
 // log normal(z | mu, s), c0 = -log(2 pi) / 2; NaN unless s is a positive finite number
 __device__ inline double lo_normal_loglik(double z, double mu, double s, double c0)

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "bdrt_nuts_launch.h"
 
@@ -207,6 +208,7 @@ struct Sampler {
     SamplerPlan plan;                 // which kernel advances the run, and with what
     SamplerEnv env;
     int n_units = 0, D = 0, n_cu = 256;
+    std::vector<int> spec;            // host copy: the spectrum of each unit (bdrt_sampler_loo: the data row of a group)
     Kernel last_one_chain = Kernel::solo;   // the kernel of the last launch in the solo layout (bdrt_sampler_kind)
     int live = 0;                     // chains of the solo layout still running (after the last launch that read the done counter)
     hipStream_t stream = nullptr;
@@ -324,6 +326,7 @@ bdrt_sampler *bdrt_sampler_create(bdrt_problem *p, int n_units, const int *spec,
         st.phase = PH_INIT;
         st.z_iter = -1;
         st.spec = spec ? spec[u] : 0;
+        S.spec.push_back(st.spec);
         st.chain_id = chain_id ? chain_id[u] : u;
         st.eps = c.stepsize0;
         st.dir = 1;
@@ -678,7 +681,7 @@ int bdrt_sampler_phase_profile(bdrt_sampler *s, int enable, long long *cycles32)
     return 0;
 }
 
-// Common front of the four reductions over a sampler's draws: units [unit_lo, unit_hi) must exist, hold draws and, with
+// Common front of the reductions over a sampler's draws: units [unit_lo, unit_hi) must exist, hold draws and, with
 // chains_per_group > 0, split into groups of that many chains.  Binds the calling thread to the sampler's device, waits for the
 // sampler's stream and gives the first draw of unit_lo in *dX.  who: the caller's name and its word for the range, which open
 // the message ("bdrt_sampler_summary: bad unit" range).
@@ -744,6 +747,83 @@ int bdrt_sampler_rank_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int
     return rank_diagnostics_to_host(dX, (long)S.np.n_draws * S.D, (long)S.D, S.prob->is_pos.data(),
                                     (unit_hi - unit_lo) / chains_per_group, chains_per_group, S.np.n_draws, S.D, p_lo, p_hi, rhat,
                                     ess_bulk, ess_tail, ess_mean, sd, S.stream);
+}
+
+// Common front of bdrt_sampler_loo and bdrt_sampler_loo_predict: argument checks, sampler_draws, and the job for the device
+// reductions (bdrt_host.h).  name: the entry point; spec: storage for the groups' spectra.
+static int sampler_loo_job(const char *name, bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0,
+                           int ncols, int reff_mode, const double *reff_in, size_t chunk_bytes, std::vector<int> &spec, LooDraws &j)
+{
+    if (!s || chains_per_group < 1 || (pair != 0 && pair != 1) || reff_mode < 0 || reff_mode > 2 || (reff_mode == 1 && !reff_in)) {
+        set_error("%s: bad arguments", name);
+        return -1;
+    }
+    Sampler &S = s->impl;
+    const int N2 = 2 * S.prob->dev.nf;
+    if (col0 < 0 || ncols < 1 || col0 + ncols > N2 || (pair && (col0 != 0 || ncols != N2))) {
+        set_error("%s: bad column range (pair = 1 needs all %d columns)", name, N2);
+        return -1;
+    }
+    const std::string who = std::string(name) + ": bad unit";
+    const double *dX;
+    if (int rc = sampler_draws(who.c_str(), s, unit_lo, unit_hi, chains_per_group, &dX)) return rc;
+    const long rows = (long)chains_per_group * S.np.n_draws;
+    if (rows > bdrt_psis_loo_max_draws()) {
+        set_error("%s: %ld draws per column, the kernel holds at most %d", name, rows, bdrt_psis_loo_max_draws());
+        return -2;
+    }
+    if (rows < 2) { set_error("%s: at least 2 draws are needed", name); return -1; }
+    const int G = (unit_hi - unit_lo) / chains_per_group;
+    spec.resize((size_t)G);
+    for (int g = 0; g < G; ++g) {
+        const int u0 = unit_lo + g * chains_per_group;
+        spec[g] = S.spec[u0];
+        for (int m = 1; m < chains_per_group; ++m)
+            if (S.spec[u0 + m] != spec[g]) { set_error("%s: the units of group %d were sampled against different spectra", name, g); return -1; }
+    }
+    j.prob = S.prob; j.draws = dX; j.spec = spec.data();
+    j.G = G; j.chains = chains_per_group; j.n_draws = S.np.n_draws;
+    j.pair = pair; j.col0 = col0; j.ncols = ncols;
+    j.reff_mode = reff_mode; j.reff_in = reff_in; j.chunk_bytes = chunk_bytes; j.stream = S.stream;
+    return 0;
+}
+
+int bdrt_sampler_loo(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols, int reff_mode,
+                     const double *reff_in, size_t chunk_bytes, double *lpd, double *elpd_loo, double *pareto_k, double *p_waic,
+                     int *n_tail, double *reff_out)
+{
+    if (!lpd || !elpd_loo || !pareto_k || !p_waic || !n_tail) { set_error("bdrt_sampler_loo: null argument"); return -1; }
+    std::vector<int> spec;
+    LooDraws j;
+    if (int rc = sampler_loo_job("bdrt_sampler_loo", s, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, reff_mode, reff_in,
+                                 chunk_bytes, spec, j))
+        return rc;
+    return loo_of_draws(j, lpd, elpd_loo, pareto_k, p_waic, n_tail, reff_out);
+}
+
+int bdrt_sampler_loo_predict(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                             int reff_mode, const double *reff_in, size_t chunk_bytes, double *mean, double *sd, double *pit,
+                             double *mean_post, double *sd_post, double *pit_post, double *pareto_k, int *n_tail, double *reff_out)
+{
+    if (!mean || !sd || !pit || !mean_post || !sd_post || !pit_post || !pareto_k || !n_tail) {
+        set_error("bdrt_sampler_loo_predict: null argument");
+        return -1;
+    }
+    std::vector<int> spec;
+    LooDraws j;
+    if (int rc = sampler_loo_job("bdrt_sampler_loo_predict", s, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, reff_mode,
+                                 reff_in, chunk_bytes, spec, j))
+        return rc;
+    return loo_predict_of_draws(j, mean, sd, pit, mean_post, sd_post, pit_post, pareto_k, n_tail, reff_out);
+}
+
+size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict)
+{
+    if (!s || chains_per_group < 1 || ncols < 1) return 0;
+    LooDraws j = {};
+    j.prob = s->impl.prob; j.chains = chains_per_group; j.n_draws = s->impl.np.n_draws;
+    j.pair = pair; j.ncols = ncols; j.reff_mode = reff_mode;
+    return loo_draws_group_bytes(j, predict != 0);
 }
 
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s)

@@ -25,7 +25,8 @@ comes from `column_diagnostics` here.
 
 Out of scope: pystan's E-BFMI check ('energy').  It needs the Hamiltonian of every draw, and no sampler kernel records it;
 `checks=['energy']` raises NotImplementedError.  Of the rank-normalised family: the MCSE of sd and of quantiles, rank plots,
-the sharded path of parallel.py, and making these checks the default of `fit` / `fit_many`.
+and making these checks the default of `fit` / `fit_many` (`parallel.sample_sharded(..., rank_diagnostics=True)` reduces them
+per rank on the sampler's device draws).
 """
 import ctypes as C
 import logging

@@ -410,8 +410,9 @@ class StanModel:
         return res
 
     def sampling(self, data, warmup=200, iter=400, chains=2, seed=1234, init='random', control=None,
-                 chain_ids=None, rounds_per_launch=None):
-        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan."""
+                 chain_ids=None, rounds_per_launch=None, loo=None):
+        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan.  loo: `sample_units`' argument; what it
+        reduces is the fit's `device_loo`."""
         P = self._prepare(data)
         n_draws = int(iter) - int(warmup)
         if n_draws < 0:
@@ -423,11 +424,15 @@ class StanModel:
         init_theta = None
         if not (init is None or (isinstance(init, str) and init == 'random')):
             init_theta = self._init_theta(init, chains, seed)
-        draws, lp, diag = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
-                                       chain_ids=chain_ids, rounds_per_launch=rounds_per_launch)
+        res = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
+                           chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo)
+        draws, lp, diag = res[:3]
         theta = draws.reshape(chains * n_draws, P.D)
-        return StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
-                       control=dict(adapt_delta=ctrl.adapt_delta, max_treedepth=ctrl.max_treedepth), warmup=warmup)
+        fit = StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
+                      control=dict(adapt_delta=ctrl.adapt_delta, max_treedepth=ctrl.max_treedepth), warmup=warmup)
+        if loo is not None:
+            fit.device_loo = res[3]
+        return fit
 
 
 class DeviceArray:
@@ -543,6 +548,18 @@ class Sampler:
         from .diagnostics import sampler_rank_diagnostics
         return sampler_rank_diagnostics(self, unit_lo, unit_hi, chains, tail_probs)
 
+    def loo(self, unit_lo, unit_hi, chains, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+        """PSIS-LOO and WAIC per observation of units [unit_lo, unit_hi), groups of `chains` consecutive units that sampled one
+        spectrum, reduced where the draws are (bdrt_sampler_loo): the dict `loo.psis_loo` returns, each entry [groups, units],
+        plus 'reff'.  Arguments: `loo.sampler_psis_loo`."""
+        from .loo import sampler_psis_loo
+        return sampler_psis_loo(self, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes)
+
+    def loo_predict(self, unit_lo, unit_hi, chains, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+        """The LOO predictive moments of the same groups (bdrt_sampler_loo_predict): `loo.psis_predict`'s dict plus 'reff'."""
+        from .loo import sampler_psis_predict
+        return sampler_psis_predict(self, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes)
+
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""
         p = self._lib.bdrt_sampler_draws_dev(self.handle)
@@ -561,16 +578,36 @@ class Sampler:
 
 
 def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, chain_ids=None, init_theta=None,
-                 rounds_per_launch=None, diagnostics_chains=None):
+                 rounds_per_launch=None, diagnostics_chains=None, loo=None):
     """Run n_units chains (unit u: spectrum spec[u], RNG stream (seed, chain_ids[u])) to completion on the GPU.
     Returns draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain diagnostics.
     diagnostics_chains=M: also reduce the convergence diagnostics of the constrained parameters, groups of M consecutive units,
-    in one launch while the sampler still holds the draws; a fourth item (mean, sd, n_eff, Rhat), each [n_units / M, D]."""
+    in one launch while the sampler still holds the draws; a fourth item (mean, sd, n_eff, Rhat), each [n_units / M, D].
+    loo=dict(chains=M, loo=True, predict=False, unit=, part=, reff=, chunk_bytes=): also reduce PSIS-LOO (`Sampler.loo`) and / or
+    the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; one more item, a dict
+    with the entries 'loo' and / or 'predict'."""
+    kw = None
+    if loo is not None:
+        kw = dict(loo)
+        unknown = sorted(set(kw) - {'chains', 'loo', 'predict', 'unit', 'part', 'reff', 'chunk_bytes'})
+        if unknown or 'chains' not in kw:
+            raise ValueError('sample_units: loo needs chains and takes loo, predict, unit, part, reff, chunk_bytes (got %s)' % sorted(kw))
+        from .loo import check_device_args
+        check_device_args(kw.get('unit', 'frequency'), kw.get('part', 'both'), kw.get('reff', 'auto'))
     with Sampler(problem, n_units, warmup, n_draws, seed, ctrl, spec=spec, chain_ids=chain_ids, init_theta=init_theta) as smp:
         smp.run(rounds_per_launch)
         res = smp.results()
         if diagnostics_chains:
             res = res + (smp.diagnostics(0, n_units, diagnostics_chains),)
+        if kw is not None:
+            args = (0, n_units, kw['chains'], kw.get('unit', 'frequency'), kw.get('part', 'both'), kw.get('reff', 'auto'),
+                    kw.get('chunk_bytes'))
+            out = {}
+            if kw.get('loo', True):
+                out['loo'] = smp.loo(*args)
+            if kw.get('predict', False):
+                out['predict'] = smp.loo_predict(*args)
+            res = res + (out,)
         return res
 
 

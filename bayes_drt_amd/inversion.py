@@ -974,7 +974,8 @@ class Inverter:
     def fit(self, frequencies, Z, part='both', scale_Z=True, nonneg=False, outliers=False, check_outliers=True,
             init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
             mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
-            model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True):
+            model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True,
+            loo=False, loo_predict=False, loo_kw=None):
         """Fit the distribution(s) with the calibrated hierarchical Bayesian model: mode='optimize' (MAP) or
         'sample' (NUTS).  Arguments as in the reference (:1072-1152), plus two that only concern mode='optimize':
 
@@ -990,8 +991,11 @@ class Inverter:
             reference's `optimizing` call returns.
         check_diagnostics : mode='sample' only -- True (default): pystan's check after sampling (n_eff, split R-hat,
             divergences, tree depth; n_eff and R-hat skipped above 1000 flat names), logged at WARNING to
-            logging.getLogger('bayes_drt_amd') (bayes_drt_amd.diagnostics); False: no check."""
+            logging.getLogger('bayes_drt_amd') (bayes_drt_amd.diagnostics); False: no check.
+        loo, loo_predict, loo_kw : mode='sample' only -- as in `fit_many`: `loo_result` / `loo_predict_result` reduced while
+            the sampler still holds the draws."""
         self._fit_argument_checks(part, mode, fitY, SA, SASY, n_starts, algorithm)
+        lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
         job = self._fit_prepare(frequencies, Z, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                 inductance_scale, outlier_lambda, mode, add_stan_data, model_str, fitY, SA, SASY, n_starts)
         model, dat = job['model'], job['dat']
@@ -1001,7 +1005,10 @@ class Inverter:
             self._opt_report = model.last_report
         else:
             self._sample_result = model.sampling(dat, warmup=warmup, iter=warmup + samples, chains=chains,
-                                                 seed=random_seed, init=job['init'], control=dict(self._NUTS_CONTROL))
+                                                 seed=random_seed, init=job['init'], control=dict(self._NUTS_CONTROL),
+                                                 loo=None if lkw is None else dict(lkw, chains=chains))
+            if lkw is not None:
+                self._store_device_loo(self._sample_result.device_loo, 0, lkw, dat, chains * samples)
             if check_diagnostics:
                 from . import diagnostics
                 diagnostics.auto_check(self._sample_result, diagnostics.flat_parameter_count(job['model_str'], dat))
@@ -1064,7 +1071,8 @@ class Inverter:
     def fit_many(self, frequencies, Z_list, part='both', scale_Z=True, nonneg=False, outliers=False, check_outliers=True,
                  init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
                  mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
-                 model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True):
+                 model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True, loo=False,
+                 loo_predict=False, loo_kw=None):
         """The fits `[copy(self).fit(frequencies, Z, ...) for Z in Z_list]` -- the reference's own workload is such a loop
         over spectra measured on one frequency grid (code_EchemActa/Run fits.ipynb cells 4-5, inversion.py:1072-1081,
         :1218-1221) -- as ONE batch: one shared problem in HBM (the matrices are those of the common grid), every
@@ -1083,8 +1091,15 @@ class Inverter:
         Returns a list of Inverter objects (shallow copies of this one) carrying the fit attributes of `fit`, readable
         through `predict_*`, `coef_percentile`, ...; this instance itself is left as it was.
         check_diagnostics (mode='sample'): pystan's check of every spectrum's chains, as `fit` runs it; the parameters of the
-        whole batch are reduced in one launch on the sampler's device draws, the transformed parameters in one more."""
+        whole batch are reduced in one launch on the sampler's device draws, the transformed parameters in one more.
+        loo / loo_predict (mode='sample'; ValueError with mode='optimize'): every view also gets `loo_result` / `loo_predict_result`,
+        what `loo_many(views, part=part, **loo_kw)` / `loo_predict_many` would store, reduced while the sampler still holds the
+        draws (`Sampler.loo`, `Sampler.loo_predict`): the draws do not go back to the device, Z_hat, sigma_tot and the log-
+        likelihoods never leave it, and inside a process group each rank reduces its own spectra.  loo_kw: dict with `unit` and
+        `reff` as in `loo` (default 'frequency', 'auto'); the part is the fit's.  With reff None or a number the results equal
+        `loo_many` on the views bit for bit; reff='auto' is reduced on the device and may differ from the host's in the last bits."""
         self._fit_argument_checks(part, mode, False, False, False, n_starts, algorithm)
+        lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
         views, jobs = self._batch_jobs(frequencies, Z_list, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                        inductance_scale, outlier_lambda, mode, add_stan_data, model_str, n_starts)
         if not views:
@@ -1097,10 +1112,46 @@ class Inverter:
             order.setdefault(self._batch_key(job), []).append(i)
         for idx in order.values():
             self._fit_batch([views[i] for i in idx], [jobs[i] for i in idx], mode, random_seed, max_iter, warmup, samples,
-                            chains, algorithm, group, check_diagnostics, idx)
+                            chains, algorithm, group, check_diagnostics, idx, lkw)
         for inv, job in zip(views, jobs):
             inv._fit_finish(job, mode, job['sigma_min'], check_outliers)
         return views
+
+    @staticmethod
+    def _loo_arguments(loo, loo_predict, loo_kw, mode, part):
+        """The `loo=` dict for the engine (None: not asked for), checked before any GPU work."""
+        if not (loo or loo_predict):
+            if loo_kw is not None:
+                raise ValueError('loo_kw is given, but neither loo nor loo_predict is set')
+            return None
+        if mode != 'sample':
+            raise ValueError("loo / loo_predict need the draws of mode='sample'; LOO of a MAP fit is not defined here")
+        from . import loo as _loo
+        return dict(_loo.check_loo_kw(loo_kw, part), loo=bool(loo), predict=bool(loo_predict), part=part)
+
+    def _store_device_loo(self, res, g, lkw, dat, S, index=None, quiet=False):
+        """Row g of the device reductions (`Sampler.loo` / `Sampler.loo_predict` dicts under 'loo' / 'predict') -> `loo_result` /
+        `loo_predict_result`, through the functions `loo_many` / `loo_predict_many` build them with."""
+        from . import loo as _loo
+        part, pair = lkw['part'], lkw['unit'] == 'frequency'
+        z = np.asarray(dat['Z'], dtype=float)
+        z = (z[g] if z.ndim == 2 else z).reshape(-1)
+        nf = len(z) // 2
+        freq = np.asarray(dat['freq'], dtype=float)
+        prefix = '' if index is None else 'fit %d: ' % index
+        was = _loo.logger.disabled
+        _loo.logger.disabled = was or quiet
+        try:
+            if 'loo' in res:
+                p = {k: v[g] for k, v in res['loo'].items()}
+                self.loo_result = _loo._result(p, 2 if pair else 1, S,
+                                               float(np.log(self._Z_scale)), freq, prefix)
+            if 'predict' in res:
+                p = {k: v[g] for k, v in res['predict'].items()}
+                zc = z if part == 'both' else (z[:nf] if part == 'real' else z[nf:])
+                self.loo_predict_result = self._loo_predict_view(_loo._predict_result(p, zc, S, freq, prefix), part, freq)
+        finally:
+            _loo.logger.disabled = was
 
     @staticmethod
     def _batch_key(job):
@@ -1186,8 +1237,9 @@ class Inverter:
 
     @staticmethod
     def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics=False,
-                   index=None):
-        """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view."""
+                   index=None, lkw=None):
+        """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view, and with `lkw`
+        (`_loo_arguments`) `loo_result` / `loo_predict_result`."""
         import ctypes as C
         from . import engine, parallel
         from ._lib import NutsControl
@@ -1264,9 +1316,11 @@ class Inverter:
             pk = dict(kw, blocks=blocks, Z=np.asarray(dat['Z'], dtype=float), freq=np.asarray(dat['freq'], dtype=float))
             want = bool(check_diagnostics and flat <= diagnostics.MAX_FLAT)
             res = parallel.sample_sharded(pk if dist.get_rank(group) == 0 else None, ns, chains, warmup, n_draws, seed=random_seed,
-                                          control=control, group=group, gather='draws', init_theta=init_theta, diagnostics=want)
+                                          control=control, group=group, gather='draws', init_theta=init_theta, diagnostics=want,
+                                          loo=None if lkw is None else {k: v for k, v in lkw.items()})
             if want:
                 param_stats = (None, None, res['n_eff'], res['Rhat'])
+            loo_res = {k2: res[k1] for k1, k2 in (('loo', 'loo'), ('loo_predict', 'predict')) if k1 in res}
             draws, lp = res['draws'], res['lp']
             diag = [dict(n_leapfrog=int(r[0]), n_divergent=int(r[1]), n_max_treedepth=int(r[2]), stepsize=float(r[3]),
                          mean_accept=float(r[4])) for r in res['stats']]
@@ -1277,15 +1331,21 @@ class Inverter:
                 setattr(ctrl, k, v)
             want = chains if (check_diagnostics and flat <= diagnostics.MAX_FLAT) else None
             res = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
-                                      init_theta=init_theta, diagnostics_chains=want)
+                                      init_theta=init_theta, diagnostics_chains=want,
+                                      loo=None if lkw is None else dict(lkw, chains=chains))
             draws, lp, diag = res[:3]
             if want:
                 param_stats = res[3]
+            loo_res = res[-1] if lkw is not None else {}
         ctl = dict(adapt_delta=control['adapt_delta'], max_treedepth=control.get('max_treedepth', 10))
         for i, inv in enumerate(views):
             u0, u1 = i * chains, (i + 1) * chains
             inv._sample_result = engine.StanFit(model, draws[u0:u1].reshape(chains * n_draws, P.D), lp[u0:u1].reshape(-1),
                                                 diag[u0:u1], chains, n_draws, control=ctl, warmup=warmup)
+            if lkw is not None:
+                # (with several ranks every rank holds the same results and only rank 0 logs)
+                inv._store_device_loo(loo_res, i, lkw, dat, chains * n_draws, i if index is None else index[i],
+                                      quiet=world > 1 and dist.get_rank(group) != 0)
         # with several ranks only rank 0 runs the check (and logs): every rank holds the same results
         if check_diagnostics and (world == 1 or dist.get_rank(group) == 0):
             diagnostics.batch_check([inv._sample_result for inv in views], flat, param_stats, index)

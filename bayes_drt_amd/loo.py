@@ -18,8 +18,18 @@ tests/loo_predict_numpy.py).  The residual (z - mean) / sd judges a point by a f
 z-score of `Inverter.check_outliers`.  Among equal log ratios in the tail the draw with the smaller index gets the smaller
 smoothed weight.
 
+On a sampler's draws (`sampler_psis_loo`, `sampler_psis_predict`; `Sampler.loo`, `Sampler.loo_predict`): the same two reductions
+where the sampler left the draws, in HBM (bdrt_sampler_loo, bdrt_sampler_loo_predict).  The batch evaluator gives Z_hat and
+sigma_tot of the draws in chunks of spectra, the kernels above reduce them against the problem's own device copy of each
+spectrum, and only the per-observation results come back.  `Inverter.fit_many(..., loo=True, loo_predict=True)` and
+`parallel.sample_sharded(..., loo=...)` use it, the latter with each rank reducing its own spectra, so that gather='summary' has
+a LOO result although no draw leaves a GPU.  With reff None, a number or an array the results equal the host path on the
+downloaded draws bit for bit (`host_psis_loo`, `host_psis_predict` are that path on stacked draws); reff='auto' is reduced on the
+device too (exp(ll - max ll) per observation, then the kernel of `column_diagnostics`), and since the device's exp is not numpy's,
+the relative efficiency may differ from `relative_efficiency` in its last bits: the result carries the 'reff' that was used.
+
 Out of scope: K-fold or exact refits and moment matching for high-k observations; LOO of MAP or ridge fits; predictive checks
-with replicated data, plots, and the sharded path of parallel.py.
+with replicated data, plots, and a `fit_many` that keeps no draws at all.
 """
 import logging
 
@@ -150,6 +160,139 @@ def psis_predict(Zhat, sig, z, unit='frequency', reff=None):
                                      *[_lib.ptr(o) for o in outs], _lib.ptr(k), _lib.ptr(n_tail)), 'bdrt_psis_predict')
     res = dict(zip(PREDICT_FIELDS, outs), pareto_k=k, n_tail=n_tail)
     return {key: v[0] for key, v in res.items()} if one else res
+
+
+# ---------------------------------------------------------------------------------------------------- on a sampler's draws
+PARTS = ('both', 'real', 'imag')
+LOO_KW = ('unit', 'reff')                            # what `fit_many(loo_kw=...)` accepts
+
+
+def check_device_args(unit='frequency', part='both', reff='auto', who='loo'):
+    """The checks of the device path that need neither a GPU nor the draws: (pair, reff mode 0 / 1 / 2).  Messages are the
+    host path's."""
+    pair = _pair(unit)
+    if part not in PARTS:
+        raise ValueError("part must be 'both', 'real' or 'imag'")
+    if pair and part != 'both':
+        raise ValueError("%s: unit='frequency' needs part='both' (a half of the columns has points for units)" % who)
+    if isinstance(reff, str):
+        if reff != 'auto':
+            raise ValueError("reff must be 'auto', None, a number or an array")
+        return pair, 2
+    if reff is not None and not np.all(np.isfinite(np.asarray(reff, dtype=float)) & (np.asarray(reff, dtype=float) > 0)):
+        raise ValueError('%s: reff must be positive and finite' % who)
+    return pair, 0 if reff is None else 1
+
+
+def check_loo_kw(loo_kw, part='both'):
+    """`fit_many(loo_kw=...)` -> dict(unit, reff), checked without a GPU.  A fit of one part has points for units, as `loo` of
+    such a fit has."""
+    kw = dict(loo_kw or {})
+    unknown = sorted(set(kw) - set(LOO_KW))
+    if unknown:
+        raise ValueError('loo_kw: unknown keys %s (known: %s)' % (unknown, list(LOO_KW)))
+    unit, reff = kw.get('unit', 'frequency'), kw.get('reff', 'auto')
+    _pair(unit)
+    check_device_args('point' if part != 'both' else unit, part, reff)
+    return dict(unit='point' if part != 'both' else unit, reff=reff)
+
+
+def chunk_or_default(chunk_bytes):
+    """`chunk_bytes` of the device path: None -> 0, the library's default (1 GiB of device scratch per chunk)."""
+    if chunk_bytes is None:
+        return 0
+    if int(chunk_bytes) < 0:
+        raise ValueError('chunk_bytes must not be negative')
+    return int(chunk_bytes)
+
+
+def _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, who, limit):
+    """Checks and the common leading arguments of the two entry points; `r` keeps the reff array alive for the call."""
+    pair, mode = check_device_args(unit, part, reff, who)
+    chains, unit_lo, unit_hi = int(chains), int(unit_lo), int(unit_hi)
+    if chains < 1 or unit_lo < 0 or unit_hi > sampler.n_units or unit_hi <= unit_lo or (unit_hi - unit_lo) % chains:
+        raise ValueError('%s: units [%d, %d) do not split into groups of %d chains' % (who, unit_lo, unit_hi, chains))
+    if sampler.n_draws < 1:
+        raise ValueError('%s: the sampler holds no draws' % who)
+    S = chains * sampler.n_draws
+    if S > limit:
+        raise ValueError('%s: %d draws per observation, the kernel holds at most %d' % (who, S, limit))
+    if S < 2:
+        raise ValueError('%s: at least 2 draws are needed' % who)
+    nf = sampler.problem.nf
+    col0, ncols = {'both': (0, 2 * nf), 'real': (0, nf), 'imag': (nf, nf)}[part]
+    G, U = (unit_hi - unit_lo) // chains, ncols // 2 if pair else ncols
+    r = None
+    if mode == 1:
+        r = _lib.f64(np.broadcast_to(np.asarray(reff, dtype=float), (G, U)))
+    front = (sampler.handle, unit_lo, unit_hi, chains, pair, col0, ncols, mode, _lib.ptr(r), chunk_or_default(chunk_bytes))
+    return front, r, G, U, ncols
+
+
+def sampler_psis_loo(sampler, unit_lo, unit_hi, chains, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+    """`psis_loo(pointwise_log_lik(...))` of the draws a sampler holds in HBM (bdrt_sampler_loo): units [unit_lo, unit_hi) in
+    groups of `chains` consecutive units that sampled one spectrum; the data are the problem's own device copy of that spectrum.
+    part: 'both', or 'real' / 'imag' for that half of the scalar observations (units are points then).  reff: 'auto' (the
+    relative efficiency of the likelihood draws, reduced on the device), None (1), a number or [G, units].  Neither the draws
+    nor Z_hat, sigma_tot or the log-likelihoods leave the device, which evaluates them in chunks of groups whose scratch stays
+    within `chunk_bytes` (None: 1 GiB).  Returns `psis_loo`'s dict, each entry [G, units], plus 'reff', what was used.  With
+    reff None, a number or an array every entry equals the host path on the downloaded draws bit for bit."""
+    front, r, G, U, _ = _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, 'psis_loo', max_draws())
+    outs = [np.empty((G, U)) for _ in range(4)]
+    n_tail, used = np.empty((G, U), dtype=np.int32), np.empty((G, U))
+    _lib.check(sampler._lib.bdrt_sampler_loo(*front, *[_lib.ptr(o) for o in outs], _lib.ptr(n_tail), _lib.ptr(used)),
+               'bdrt_sampler_loo')
+    lpd, elpd, k, pw = outs
+    return {'lpd': lpd, 'elpd_loo': elpd, 'p_loo': lpd - elpd, 'pareto_k': k, 'p_waic': pw, 'elpd_waic': lpd - pw,
+            'n_tail': n_tail, 'reff': used}
+
+
+def sampler_psis_predict(sampler, unit_lo, unit_hi, chains, unit='frequency', part='both', reff='auto', chunk_bytes=None):
+    """`psis_predict` of the draws a sampler holds in HBM (bdrt_sampler_loo_predict); arguments as `sampler_psis_loo`.  Returns
+    `psis_predict`'s dict -- the six per-scalar entries [G, columns of the part], pareto_k and n_tail [G, units] -- plus
+    'reff'."""
+    front, r, G, U, ncols = _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes,
+                                           'psis_predict', predict_max_draws())
+    outs = [np.empty((G, ncols)) for _ in PREDICT_FIELDS]
+    k, n_tail, used = np.empty((G, U)), np.empty((G, U), dtype=np.int32), np.empty((G, U))
+    _lib.check(sampler._lib.bdrt_sampler_loo_predict(*front, *[_lib.ptr(o) for o in outs], _lib.ptr(k), _lib.ptr(n_tail),
+                                                     _lib.ptr(used)), 'bdrt_sampler_loo_predict')
+    return dict(zip(PREDICT_FIELDS, outs), pareto_k=k, n_tail=n_tail, reff=used)
+
+
+def _host_arrays(problem, draws, z, part):
+    """Z_hat, sigma_tot [G, S, columns] and z [G, columns] of host-resident unconstrained draws [G, S, D]: `transformed` per
+    group, as `StanFit['Z_hat']` calls it, then the columns of the part."""
+    draws, z = np.asarray(draws, dtype=float), np.atleast_2d(np.asarray(z, dtype=float))
+    if draws.ndim != 3 or z.shape[0] != draws.shape[0]:
+        raise ValueError('draws must be [G, S, D] and z [G, 2 Nf]')
+    nf = z.shape[1] // 2
+    cols = {'both': slice(0, 2 * nf), 'real': slice(0, nf), 'imag': slice(nf, 2 * nf)}[part]
+    tr = [problem.transformed(d)[1:] for d in draws]
+    return (np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
+            np.ascontiguousarray(np.stack([t[1] for t in tr])[:, :, cols]), np.ascontiguousarray(z[:, cols]))
+
+
+def host_psis_loo(problem, draws, z, chains, unit='frequency', part='both', reff='auto'):
+    """What `sampler_psis_loo` computes, on host-resident draws [G, chains * n_draws, D] against z [G, 2 Nf] through the host-
+    staged entry points (`Problem.transformed`, `pointwise_log_lik`, `psis_loo`): the yardstick of the device path, and what
+    `parallel.sample_sharded` runs when the chains of a spectrum are spread over ranks.  reff='auto' is
+    `relative_efficiency`."""
+    check_device_args(unit, part, reff, 'psis_loo')
+    Zh, sg, zz = _host_arrays(problem, draws, z, part)
+    ll = pointwise_log_lik(Zh, sg, zz, unit)
+    r = np.broadcast_to(np.asarray(1.0 if reff is None else _reff_arg(reff, ll, int(chains)), dtype=float), ll[:, 0].shape)
+    return dict(psis_loo(ll, r), reff=np.array(r))
+
+
+def host_psis_predict(problem, draws, z, chains, unit='frequency', part='both', reff='auto'):
+    """The same for `sampler_psis_predict` (`psis_predict`)."""
+    pair, _ = check_device_args(unit, part, reff, 'psis_predict')
+    Zh, sg, zz = _host_arrays(problem, draws, z, part)
+    U = zz.shape[1] // 2 if pair else zz.shape[1]
+    r = np.broadcast_to(np.asarray(1.0 if reff is None else _predict_reff(reff, Zh, sg, zz, pair, int(chains)), dtype=float),
+                        (len(zz), U))
+    return dict(psis_predict(Zh, sg, zz, unit, r), reff=np.array(r))
 
 
 def relative_efficiency(ll, chains):

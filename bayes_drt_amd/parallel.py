@@ -190,6 +190,38 @@ class GpuWorker:
         """(mean, sd, n_eff, Rhat) [spectra x D] of this rank's units [unit_lo, unit_hi), reduced on the sampler's device draws."""
         return self.sampler.diagnostics(unit_lo, unit_hi, chains)
 
+    def rank_diagnostics(self, unit_lo, unit_hi, chains):
+        """Rank-normalised diagnostics (dict, each [spectra x D]) of this rank's units, reduced on the sampler's device draws."""
+        return self.sampler.rank_diagnostics(unit_lo, unit_hi, chains)
+
+    def loo(self, unit_lo, unit_hi, chains, **kw):
+        """PSIS-LOO per observation (`Sampler.loo`: dict, each [spectra x units]) of this rank's units, reduced on the device."""
+        return self.sampler.loo(unit_lo, unit_hi, chains, **kw)
+
+    def loo_predict(self, unit_lo, unit_hi, chains, **kw):
+        """The LOO predictive moments (`Sampler.loo_predict`) of this rank's units, reduced on the device."""
+        return self.sampler.loo_predict(unit_lo, unit_hi, chains, **kw)
+
+    @staticmethod
+    def reduce_rank_diagnostics(blocks, chains, is_pos):
+        """The same reduction on host-resident unconstrained draws [spectra, chains * draws, D] (bdrt_rank_diagnostics)."""
+        from .diagnostics import rank_diagnostics
+        return rank_diagnostics(blocks, chains, is_pos=is_pos)
+
+    @staticmethod
+    def reduce_loo(problem_kwargs, blocks, chains, predict, **kw):
+        """`loo` / `loo_predict` on host-resident unconstrained draws [spectra, chains * draws, D]: the host path
+        (`loo.host_psis_loo` / `loo.host_psis_predict`) against the spectra of `problem_kwargs`."""
+        from . import loo as _loo
+        from .model import Problem
+        pk = dict(problem_kwargs)
+        bl = pk.pop('blocks'); Z = np.atleast_2d(pk.pop('Z')); freq = pk.pop('freq')
+        prob = Problem(bl, Z, freq, **pk)
+        try:
+            return (_loo.host_psis_predict if predict else _loo.host_psis_loo)(prob, blocks, Z, chains, **kw)
+        finally:
+            prob.close()
+
     @staticmethod
     def reduce_diagnostics(blocks, chains, is_pos):
         """The same reduction on host-resident unconstrained draws [spectra, chains * draws, D] (bdrt_diagnostics)."""
@@ -246,8 +278,47 @@ def _unpack_problem(flat):
     return kw
 
 
+_RANK_FIELDS = ('rhat', 'ess_bulk', 'ess_tail', 'ess_mean', 'sd')
+_LOO_FIELDS = ('lpd', 'elpd_loo', 'pareto_k', 'p_waic', 'n_tail', 'reff')
+
+
+def _loo_jobs(loo_kw):
+    """[(result key, predict)] of the reductions `loo=` asks for."""
+    if loo_kw is None:
+        return []
+    return [(k, p) for k, p, on in (('loo', False, loo_kw.get('loo', True)), ('loo_predict', True, loo_kw.get('predict', False)))
+            if on]
+
+
+def _loo_call_kw(loo_kw, s_lo, s_hi):
+    """Keyword arguments of `Sampler.loo` for spectra [s_lo, s_hi): an array reff [n_spectra, units] is cut to their rows."""
+    kw = dict(unit=loo_kw.get('unit', 'frequency'), part=loo_kw.get('part', 'both'), reff=loo_kw.get('reff', 'auto'),
+              chunk_bytes=loo_kw.get('chunk_bytes'))
+    r = kw['reff']
+    if r is not None and not isinstance(r, str) and np.ndim(r) == 2:
+        kw['reff'] = np.asarray(r, dtype=float)[s_lo:s_hi]
+    return kw
+
+
+def _gather_fields(r, rows, group, predict):
+    """All-gather the per-spectrum rows of a `Sampler.loo` / `Sampler.loo_predict` dict, every field side by side in one
+    collective (n_tail travels as a float: exact).  rows[r]: spectra of rank r, at least one each."""
+    from .loo import PREDICT_FIELDS
+    names = (PREDICT_FIELDS + ('pareto_k', 'n_tail', 'reff')) if predict else _LOO_FIELDS
+    w = [r[k].shape[1] for k in names]
+    full = gather_rows(np.concatenate([np.asarray(r[k], dtype=np.float64) for k in names], axis=1), rows, group)
+    out, o = {}, 0
+    for k, wk in zip(names, w):
+        out[k] = full[:, o:o + wk].astype(np.int32) if k == 'n_tail' else np.ascontiguousarray(full[:, o:o + wk])
+        o += wk
+    if not predict:
+        out['p_loo'], out['elpd_waic'] = out['lpd'] - out['elpd_loo'], out['lpd'] - out['p_waic']
+    return out
+
+
 def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234, control=None, group=None,
-                   worker_cls=None, gather='draws', q=(2.5, 50.0, 97.5), init_theta=None, diagnostics=False):
+                   worker_cls=None, gather='draws', q=(2.5, 50.0, 97.5), init_theta=None, diagnostics=False, loo=None,
+                   rank_diagnostics=False):
     """Sample `chains` chains for each of `n_spectra` spectra on all ranks of the process group.
 
     problem_kwargs (needed on rank 0 only; other ranks may pass None): dict(blocks=[...], Z=[n_spectra x 2nf], freq=...,
@@ -263,9 +334,19 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
     sampler's own random starts); each rank receives the rows of its units with the scatter of the spectra.
     diagnostics=True adds n_eff [n_spectra, D] and Rhat [n_spectra, D]: the convergence diagnostics of the constrained
     parameters per spectrum (bayes_drt_amd.diagnostics), each rank reducing its own spectra in one launch on its sampler's
-    device draws; when the chains of a spectrum are spread over ranks, every rank reduces the gathered draws instead."""
+    device draws; when the chains of a spectrum are spread over ranks, every rank reduces the gathered draws instead.
+    rank_diagnostics=True adds 'rank', the dict of `diagnostics.rank_diagnostics` (each entry [n_spectra, D]), the same way.
+    loo=dict(loo=True, predict=False, unit='frequency', part='both', reff='auto', chunk_bytes=None) (given on every rank, like
+    `gather` and `q`) adds 'loo', the dict of `loo.psis_loo` plus 'reff', each entry [n_spectra, units], and / or 'loo_predict',
+    the dict of `loo.psis_predict` plus 'reff': each rank reduces its own spectra on its sampler's device draws
+    (`Sampler.loo`, `Sampler.loo_predict`) and only these rows travel, so gather='summary' has them without any draw leaving a
+    GPU; when the chains of a spectrum are spread over ranks, every rank reduces the gathered draws through the host path
+    (`loo.host_psis_loo`).  With reff None, a number or an array [n_spectra, units] the two ways agree bit for bit, so the result
+    does not depend on the world size; reff='auto' is the device's relative efficiency in the first case and
+    `loo.relative_efficiency` in the second, which may differ in the last bits of 'reff' ('reff' says what was used)."""
     if gather not in ('draws', 'summary'):
         raise ValueError("gather must be 'draws' or 'summary'")
+    loo_kw = None if loo is None else dict(loo)
     dist = _dist()
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     spec, chain = make_units(n_spectra, chains)
@@ -300,6 +381,19 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
                 if init_theta.shape[1] != D0:
                     raise ValueError('sample_sharded: init_theta has %d columns, the model has D = %d parameters'
                                      % (init_theta.shape[1], D0))
+            if loo_kw is not None:
+                from . import loo as _loo
+                unknown = sorted(set(loo_kw) - {'loo', 'predict', 'unit', 'part', 'reff', 'chunk_bytes'})
+                if unknown:
+                    raise ValueError('sample_sharded: unknown loo keys %s' % unknown)
+                pair, mode = _loo.check_device_args(loo_kw.get('unit', 'frequency'), loo_kw.get('part', 'both'),
+                                                    loo_kw.get('reff', 'auto'), 'sample_sharded')
+                _loo.chunk_or_default(loo_kw.get('chunk_bytes'))
+                if mode == 1:
+                    ncols = Zfull.shape[1] if loo_kw.get('part', 'both') == 'both' else Zfull.shape[1] // 2
+                    np.broadcast_to(np.asarray(loo_kw['reff'], dtype=float), (n_spectra, ncols // 2 if pair else ncols))
+                if chains * n_draws > _loo.max_draws() or chains * n_draws < 2:
+                    raise ValueError('sample_sharded: loo needs 2 ... %d draws per spectrum, not %d' % (_loo.max_draws(), chains * n_draws))
             if whole:
                 flat0.pop('kw_Z')
                 flat0['Z_width'] = np.array(Zfull.shape[1])
@@ -340,6 +434,10 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
                      draws=np.zeros((0, n_draws, 0)))
         if diagnostics:
             empty.update(n_eff=np.zeros((0, 0)), Rhat=np.zeros((0, 0)))
+        if rank_diagnostics:
+            empty['rank'] = {}
+        if loo_kw is not None:
+            empty.update({k: {} for k, on in (('loo', loo_kw.get('loo', True)), ('loo_predict', loo_kw.get('predict', False))) if on})
         return empty
     dd = [(D, np.asarray(worker.is_pos(), dtype=bool).tolist()) if worker is not None else None]
     dist.broadcast_object_list(dd, src=owners[0], group=group)
@@ -367,6 +465,18 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
                 dl[:, 0], dl[:, 1] = ne, rh
             dg = gather_rows(dl, [c // chains for c in counts], group)
             out['n_eff'], out['Rhat'] = dg[:, 0], dg[:, 1]
+        if rank_diagnostics:
+            from .diagnostics import _rank_dict
+            rl = np.zeros((ns_local, 5, D))
+            r = worker.rank_diagnostics(0, u1 - u0, chains)
+            for k, name in enumerate(_RANK_FIELDS):
+                rl[:, k] = r[name]
+            rg = gather_rows(rl, [c // chains for c in counts], group)
+            out['rank'] = _rank_dict(*[rg[:, k] for k in range(5)])
+        for key, predict in _loo_jobs(loo_kw):
+            lk = _loo_call_kw(loo_kw, u0 // chains, u1 // chains)
+            r = (worker.loo_predict if predict else worker.loo)(0, u1 - u0, chains, **lk)
+            out[key] = _gather_fields(r, [c // chains for c in counts], group, predict)
     else:
         # the chains of a spectrum are on several ranks: reduce the gathered draws (every rank, same arithmetic)
         mean = np.empty((n_spectra, D)); pct = np.empty((n_spectra, len(q), D))
@@ -377,6 +487,12 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
         if diagnostics:
             blocks = out['draws'].reshape(n_spectra, chains * n_draws, D)
             _, _, out['n_eff'], out['Rhat'] = cls.reduce_diagnostics(blocks, chains, is_pos)
+        if rank_diagnostics:
+            out['rank'] = cls.reduce_rank_diagnostics(out['draws'].reshape(n_spectra, chains * n_draws, D), chains, is_pos)
+        for key, predict in _loo_jobs(loo_kw):
+            lk = _loo_call_kw(loo_kw, 0, n_spectra)
+            lk.pop('chunk_bytes')
+            out[key] = cls.reduce_loo(kw, out['draws'].reshape(n_spectra, chains * n_draws, D), chains, predict, **lk)
         if gather == 'summary':
             out.pop('draws')
     if worker is not None:

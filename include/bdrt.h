@@ -380,6 +380,30 @@ int bdrt_psis_predict(const double *Zhat, const double *sig, const double *z, in
                       double *mean, double *sd, double *pit, double *mean_post, double *sd_post, double *pit_post,
                       double *pareto_k, int *n_tail);
 int bdrt_psis_predict_max_draws(void);
+/* The same two reductions on the draws a sampler holds on the device: neither the draws nor Z_hat, sigma_tot or the
+ * log-likelihoods travel; only the per-observation results come back.  A group is chains_per_group consecutive units of
+ * [unit_lo, unit_hi) that sampled ONE spectrum; its S = chains_per_group * n_draws rows are in the order the host path sees
+ * them, chain-major.  2 <= S <= bdrt_psis_loo_max_draws() (-2 above).  Per chunk of groups the batch evaluator (the launch of
+ * bdrt_transformed, without spec) gives Z_hat and sigma_tot of the rows where they are, and the kernels of
+ * bdrt_pointwise_loglik, bdrt_psis_loo / bdrt_psis_predict reduce them against the data of a group: the problem's own device
+ * copy of the group's spectrum, scalar observations [col0, col0 + ncols) of the 2 Nf (the real half, the imaginary half or
+ * all; pair = 1 needs all).  U = ncols / 2 (pair = 1) or ncols units per group.
+ *   reff_mode 0: reff = 1.  1: reff_in [G][U] (host).  2: the relative efficiency of the likelihood draws: per unit
+ *     n_eff(exp(ll - max ll)) / S with chains_per_group chains (the kernel of bdrt_diagnostics), 1 where that is not a positive
+ *     finite number.  reff_out [G][U] (may be NULL) returns what was used in every mode.
+ *   chunk_bytes: one chunk's device scratch -- per draw row the parameters, Z_hat, sigma_tot, lp and what the reduction stages
+ *     (bdrt_sampler_loo_group_bytes per group) -- stays within it; 0: 1 GiB.  A group that alone exceeds it is a chunk of one.
+ * Outputs on the host as bdrt_psis_loo's [G][U] and bdrt_psis_predict's ([G][ncols] per scalar, [G][U] per unit).  With
+ * reff_mode 0 and 1 every output equals the host-staged entry points on the downloaded draws bit for bit (a row's Z_hat and
+ * sigma_tot do not depend on its place in the evaluator's launch; a column's results do not depend on the launch). */
+int bdrt_sampler_loo(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols, int reff_mode,
+                     const double *reff_in, size_t chunk_bytes, double *lpd, double *elpd_loo, double *pareto_k, double *p_waic,
+                     int *n_tail, double *reff_out);
+int bdrt_sampler_loo_predict(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                             int reff_mode, const double *reff_in, size_t chunk_bytes, double *mean, double *sd, double *pit,
+                             double *mean_post, double *sd_post, double *pit_post, double *pareto_k, int *n_tail, double *reff_out);
+/* device bytes one group adds to a chunk of the two entry points above (predict != 0: of bdrt_sampler_loo_predict); 0: bad arguments */
+size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
