@@ -76,6 +76,11 @@ class NewtonState(C.Structure):
                 ('need_hess', C.c_int), ('n_evals', C.c_int), ('pad', C.c_int)]
 
 
+class QpFactorRecord(C.Structure):
+    """bdrt_qp_factor_record: what the box-QP solver's ladder committed for one problem (bdrt_debug_qp_factor_solve)"""
+    _fields_ = [('ok', C.c_int), ('rungs', C.c_int), ('reg', C.c_double)]
+
+
 # every symbol include/bdrt.h declares (tests/test_abi.py checks the library exports each of them)
 SYMBOLS = [
     'bdrt_build_A', 'bdrt_build_A_basis', 'bdrt_build_L', 'bdrt_build_L_rect', 'bdrt_build_M',
@@ -94,7 +99,7 @@ SYMBOLS = [
     'bdrt_sampler_loo', 'bdrt_sampler_loo_predict', 'bdrt_sampler_loo_group_bytes',
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
-    'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept',
+    'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept', 'bdrt_debug_qp_factor_solve',
 ]
 
 
@@ -209,6 +214,7 @@ def load_library():
     lib.bdrt_debug_newton_solve.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp,
                                             C.POINTER(NewtonSolveRecord)]
     lib.bdrt_debug_newton_accept.argtypes = [C.POINTER(NewtonState), vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int]
+    lib.bdrt_debug_qp_factor_solve.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(QpFactorRecord), vp, vp, vp]
     lib.bdrt_pointwise_loglik.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.bdrt_psis_loo.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.bdrt_psis_loo_max_draws.argtypes = []

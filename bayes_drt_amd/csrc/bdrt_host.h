@@ -258,6 +258,15 @@ int newton_solve_at(const double *H, const double *g, const double *x, int D, do
 int newton_accept_at(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t, const double *gt,
                      const double *tz, const double *held, double floor_x, int o_x, int Kx);
 
+// the dynamic LDS of the kernels around the box-QP solver (bdrt_qp.hip: bdrt_qp_box_batch, bdrt_ridge_ex, bdrt_debug_qp_factor_solve)
+// for n unknowns and `extra` doubles of the kernel's own: whether the packed KKT triangle lives in LDS (else in a global work
+// buffer), the bytes to ask for, and whether the launch is possible at all
+struct QpLds {
+    bool in_lds, fits;
+    size_t bytes;
+};
+QpLds qp_lds_plan(int n, size_t extra);
+
 }  // namespace bdrt
 
 struct bdrt_problem {

@@ -10,11 +10,10 @@
 // itself computed (stored in the reference's pickled fits) to 1e-8 (tests/test_ridge_reference.py).
 //
 // One workgroup (512 threads) per problem; problems of a batch run concurrently (Re-Im cross-validation: 62 fits).  The
-// KKT matrix lives in LDS as a column-major packed lower triangle (n <= 200: 157 KiB) -- or in a global work buffer for
-// larger n -- and is factored by a right-looking Cholesky (two barriers per column; the trailing update is a 32 x 16
-// thread tiling with conflict-free column walks).  The two triangular solves of a Newton direction are sequential by
-// nature: one wavefront does them with wave-level synchronisation only (a barrier per unknown would cost more than the
-// arithmetic).
+// KKT matrix lives in LDS as a column-major packed lower triangle (qp_lds_plan: n <= 185 for the plain QP, n <= 180 under the
+// ridge kernel's own vectors; 156.5 KiB and 157.3 KiB there) -- or in a global work buffer for larger n -- and is factored by a
+// blocked right-looking Cholesky (chol_packed); the two triangular solves of a Newton direction are blocked the same way
+// (chol_solve_blocked).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -87,7 +86,7 @@ __device__ __forceinline__ int cidx(int i, int j, int n) { return j * n - ((j * 
 //   (a) the 16 x 16 diagonal block by wavefront 0 on a register copy, lane r = row r; the scaled column reaches the other lanes
 //       through a 16-double LDS buffer (one round trip per column);
 //   (b) the rows below by forward substitution against the block, one row per thread;
-//   (c) the trailing triangle on v_mfma_f64_16x16x4 tiles, operands and accumulators straight from the packed triangle.
+//   (c) the trailing triangle on v_mfma_f64_16x16x4 tiles, operands and cells straight from the packed triangle.
 // Three barriers per block.  `scr`: 32 doubles of scratch.
 // LDSM: M is in LDS -- addressed as such (through a generic pointer every access is a flat load: several times the latency)
 template <bool LDSM>
@@ -125,7 +124,13 @@ __device__ __noinline__ bool chol_packed(double *M, double *diag, int n, double 
                 double inv = __builtin_amdgcn_rsq(d);
                 inv = inv * (1.5 - 0.5 * d * inv * inv);
                 inv = inv * (1.5 - 0.5 * d * inv * inv);
-                if (tid == c) { diag[j0 + c] = d * inv; s_inv[c] = inv; }
+                if (tid == c) {
+                    // sqrt(d) = d * inv, then one correction from the residual d - g^2 (an FMA gives it exactly): g^2 matches the
+                    // pivot to an ulp or two, where d * inv alone carries the error of inv twice over
+                    const double g = d * inv;
+                    diag[j0 + c] = fma(0.5 * inv, fma(-g, g, d), g);
+                    s_inv[c] = inv;
+                }
                 if (mine && k > c) {
                     const double lr = s_tile[r * 17 + c] * inv, lk = s_tile[k * 17 + c] * inv;
                     mineval -= lr * lk;
@@ -174,19 +179,23 @@ __device__ __noinline__ bool chol_packed(double *M, double *diag, int n, double 
                     xa[u] = ia < n ? LD(cidx(ia, j0 + 4 * u + kq, n)) : 0.0;
                     xb[u] = ib < n ? LD(cidx(ib, j0 + 4 * u + kq, n)) : 0.0;
                 }
-                d4 acc;
+                // the block's sixteen products are summed from zero and leave the cell in one subtraction: one rounding on the scale
+                // of the cell per block.  (Accumulated onto the cell itself every product rounds on that scale -- sixteen times as
+                // many; where the diagonal dominates, as under a barrier term z / s, the factor's residual was 4 .. 7 times LAPACK's.)
+                d4 acc = {0.0, 0.0, 0.0, 0.0};
                 bool own[4];
+                double cell[4];
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const int ri = R0 + kq + 4 * rr, ci = C0 + col;
                     own[rr] = ri < n && ci <= ri;
-                    acc[rr] = own[rr] ? LD(cidx(ri, ci, n)) : 0.0;
+                    cell[rr] = own[rr] ? LD(cidx(ri, ci, n)) : 0.0;
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) acc = mfma_f64(-xa[u], xb[u], acc);
+                for (int u = 0; u < 4; ++u) acc = mfma_f64(xa[u], xb[u], acc);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr)
-                    if (own[rr]) ST(cidx(R0 + kq + 4 * rr, C0 + col, n), acc[rr]);
+                    if (own[rr]) ST(cidx(R0 + kq + 4 * rr, C0 + col, n), cell[rr] - acc[rr]);
             }
             __syncthreads();
         }
@@ -273,6 +282,44 @@ __device__ __noinline__ void chol_solve_blocked(const double *M, const double *d
     }
 }
 
+// M <- the packed lower triangle of sym(P) + diag(dgv(i)) + reg I, factored in place by chol_packed: reg = 0 first, then the
+// ladder 1e-14 (1 + |M(0,0)|), x 100 per rung while reg <= 1e6, until a factorisation runs to completion.  P [n x n] row-major in
+// global memory (not necessarily symmetric); red: 32 doubles of scratch.  Returns (uniformly) whether a rung factored; *reg_out,
+// *rungs_out (null: not wanted): the reg last added and the number of factorisations tried.  All threads must call.
+template <bool LDSM, class DG>
+__device__ inline bool qp_factor(const double *__restrict__ P, int n, double *M, double *diag, double *red, DG dgv, QpProf &pf,
+                                 double *reg_out, int *rungs_out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double reg = 0.0;
+    bool ok = false;
+    int rungs = 0;
+    while (true) {
+        __syncthreads();
+        pf.mark(3);
+        for (int j = wave; j < n; j += QP_NT / 64) {              // one wavefront per column of the lower triangle
+            double *colj = M + cidx(j, j, n);
+            for (int i = j + lane; i < n; i += 64) {
+                double v = 0.5 * (P[(size_t)i * n + j] + P[(size_t)j * n + i]);
+                if (i == j) v += dgv(i) + reg;
+                colj[i - j] = v;
+            }
+        }
+        __syncthreads();
+        pf.mark(0);
+        const double m00 = M[0] - reg;
+        ok = chol_packed<LDSM>(M, diag, n, red);
+        ++rungs;
+        pf.mark(1);
+        if (ok) break;
+        reg = reg == 0.0 ? 1e-14 * (1.0 + fabs(m00)) : reg * 100.0;
+        if (!(reg <= 1e6)) break;                                  // (also leaves on NaN: non-finite input must not spin here)
+    }
+    if (reg_out) *reg_out = reg;
+    if (rungs_out) *rungs_out = rungs;
+    return ok;
+}
+
 // One box-constrained QP by the calling workgroup: P [n x n] and q [n] in global memory, the solution is left in sh[0..n)
 // (LDS) and, when xout != nullptr, copied there.  sh: (QP_NVEC + 1) * np + 32 doubles of LDS followed (LDSM) by the packed
 // KKT triangle; Mwork: the triangle when it lives in a global work buffer.  Returns the iteration count, -3 (KKT matrix not
@@ -322,29 +369,7 @@ __device__ inline int qp_box_solve(const double *__restrict__ P, const double *_
     // factor sym(P) + diag(dgv[i]) (+ reg I when only semi-definite); dgv: unit = 1 on bounded variables, else z/s
     QpProf pf;
     auto factor = [&](bool unit) -> bool {
-        double reg = 0.0;
-        bool ok = false;
-        while (true) {
-            __syncthreads();
-            pf.mark(3);
-            for (int j = wave; j < n; j += QP_NT / 64) {              // one wavefront per column of the lower triangle
-                double *colj = M + cidx(j, j, n);
-                for (int i = j + lane; i < n; i += 64) {
-                    double v = 0.5 * (P[(size_t)i * n + j] + P[(size_t)j * n + i]);
-                    if (i == j) v += (bd[i] != 0.0 ? (unit ? 1.0 : z[i] / s[i]) : 0.0) + reg;
-                    colj[i - j] = v;
-                }
-            }
-            __syncthreads();
-            pf.mark(0);
-            const double m00 = M[0] - reg;
-            ok = chol_packed<LDSM>(M, diag, n, red);
-            pf.mark(1);
-            if (ok) break;
-            reg = reg == 0.0 ? 1e-14 * (1.0 + fabs(m00)) : reg * 100.0;
-            if (!(reg <= 1e6)) break;                                  // (also leaves on NaN: non-finite input must not spin here)
-        }
-        return ok;
+        return qp_factor<LDSM>(P, n, M, diag, red, [&](int i) { return bd[i] != 0.0 ? (unit ? 1.0 : z[i] / s[i]) : 0.0; }, pf, nullptr, nullptr);
     };
 
     // ---- starting point: (P + diag(b)) x = -q + b lo; s = x - lo, z = -s, both shifted into the interior ----
@@ -642,6 +667,62 @@ __global__ __launch_bounds__(QP_NT) void ridge_kernel(RidgeArgs a)
     if (tid == 0) { a.cost[b] = cost; a.fun[b] = fun; a.iters[b] = it; a.flags[b] = flag; }
 }
 
+// ---- debug (tests): the production form-KKT loop, ladder, factorisation and substitutions on supplied data ---------------------
+// One workgroup per problem b: M = sym(P[b]) + diag(dg[b]) through qp_factor, then chol_solve_blocked once per right-hand side
+// on that factor.  LDS as qp_box_solve lays it out (v in the slot of x, 1 / diag in the slot of rhs, diag, red, triangle).
+// ok, rungs, reg [nb]; a problem that does not factor writes nothing else.  L [nb][n][n]: the factor as a dense lower triangle,
+// diag[] on its diagonal, zeros above; piv [nb][n]: what M(j, j) keeps; sol [nb][nrhs][n].
+template <bool LDSM>
+__global__ __launch_bounds__(QP_NT) void qp_factor_solve_kernel(const double *__restrict__ Pall, const double *__restrict__ dgall, int n,
+                                                                const double *__restrict__ rhsall, int nrhs, double *__restrict__ work,
+                                                                int *__restrict__ okall, int *__restrict__ rungsall, double *__restrict__ regall,
+                                                                double *__restrict__ Lall, double *__restrict__ pivall, double *__restrict__ solall)
+{
+    extern __shared__ __attribute__((aligned(16))) double sh[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int np = (n + 1) & ~1;
+    const size_t msize = (size_t)n * (n + 1) / 2;
+    double *v = sh, *rd = sh + 4 * np, *diag = sh + QP_NVEC * np, *red = diag + np;
+    double *M = LDSM ? red + 32 : work + (size_t)b * msize;
+    const double *P = Pall + (size_t)b * n * n, *dg = dgall + (size_t)b * n;
+    QpProf pf;
+    double reg;
+    int rungs;
+    const bool ok = qp_factor<LDSM>(P, n, M, diag, red, [&](int i) { return dg[i]; }, pf, &reg, &rungs);
+    if (tid == 0) { okall[b] = ok ? 1 : 0; rungsall[b] = rungs; regall[b] = reg; }
+    if (!ok) return;
+    double *L = Lall + (size_t)b * n * n;
+    for (size_t e = tid; e < (size_t)n * n; e += QP_NT) {
+        const int i = (int)(e / n), j = (int)(e - (size_t)i * n);
+        L[e] = j < i ? M[cidx(i, j, n)] : (j == i ? diag[i] : 0.0);
+    }
+    for (int i = tid; i < n; i += QP_NT) pivall[(size_t)b * n + i] = M[cidx(i, i, n)];
+    for (int r = 0; r < nrhs; ++r) {
+        const size_t o = ((size_t)b * nrhs + r) * n;
+        for (int i = tid; i < n; i += QP_NT) v[i] = rhsall[o + i];
+        __syncthreads();
+        chol_solve_blocked<LDSM>(M, diag, n, v, rd, red);
+        for (int i = tid; i < n; i += QP_NT) solall[o + i] = v[i];
+        __syncthreads();
+    }
+}
+
+// The dynamic LDS of a kernel around qp_box_solve and whether the packed KKT triangle lives there: the QP's vectors, diag and
+// reduction scratch, `extra` doubles of the caller's own, and the triangle when all of it stays within the 160 KiB of a workgroup
+// less QP_STATIC_LDS (chol_packed's static tile, rounded up).  fits: the launch is possible at all.
+constexpr size_t QP_STATIC_LDS = 2560, QP_LDS_TOTAL = 160 * 1024;
+QpLds qp_lds_plan(int n, size_t extra)
+{
+    const int np = (n + 1) & ~1;
+    const size_t msize = (size_t)n * (n + 1) / 2;
+    const size_t vec = (size_t)(QP_NVEC + 1) * np + 32 + extra;
+    QpLds r;
+    r.in_lds = (vec + msize) * sizeof(double) <= QP_LDS_TOTAL - QP_STATIC_LDS;
+    r.bytes = (vec + (r.in_lds ? msize : 0)) * sizeof(double);
+    r.fits = r.bytes + QP_STATIC_LDS <= QP_LDS_TOTAL;
+    return r;
+}
+
 }  // namespace bdrt
 
 using namespace bdrt;
@@ -653,12 +734,11 @@ int bdrt_qp_box_batch(const double *P, const double *q, const double *lo, int n,
 {
     if (!P || !q || !x || n < 1 || nb < 1) { set_error("bdrt_qp_box_batch: bad arguments"); return -1; }
     bind_process_device();
-    const int np = (n + 1) & ~1;
-    const size_t vec_bytes = ((size_t)(QP_NVEC + 1) * np + 32) * sizeof(double);      // + diag, reduction scratch
     const size_t msize = (size_t)n * (n + 1) / 2;
-    const bool in_lds = vec_bytes + msize * sizeof(double) <= 160 * 1024 - 2560;      // (2.5 KB of static LDS in chol_packed)
-    const size_t lds = in_lds ? vec_bytes + msize * sizeof(double) : vec_bytes;
-    if (lds + 2560 > 160 * 1024) { set_error("bdrt_qp_box_batch: n = %d too large", n); return -2; }      // (+ chol_packed's static LDS)
+    const QpLds plan = qp_lds_plan(n, 0);
+    const bool in_lds = plan.in_lds;
+    const size_t lds = plan.bytes;
+    if (!plan.fits) { set_error("bdrt_qp_box_batch: n = %d too large", n); return -2; }
     DevBuf<double> dP, dq, dlo, dx, dobj, dwork;
     DevBuf<int> dit;
     if (upload(dP, P, (size_t)nb * n * n) || upload(dq, q, (size_t)nb * n) || (lo && upload(dlo, lo, (size_t)n))) return -10;
@@ -711,10 +791,10 @@ int bdrt_ridge_ex(const bdrt_ridge_options *opt, const unsigned char *zero_delta
     bind_process_device();
     const int n = opt->n, K = opt->K, np = (n + 1) & ~1, mi = opt->max_iter;
     const size_t msize = (size_t)n * (n + 1) / 2;
-    const size_t vec = (size_t)(QP_NVEC + 1) * np + 32, extra = (size_t)6 * np + 32 + 2;
-    const bool in_lds = (vec + msize + extra) * sizeof(double) <= 160 * 1024 - 2560;
-    const size_t lds = (vec + (in_lds ? msize : 0) + extra) * sizeof(double);
-    if (lds + 2560 > 160 * 1024) { set_error("bdrt_ridge: n = %d too large", n); return -2; }      // (+ chol_packed's static LDS)
+    const QpLds plan = qp_lds_plan(n, (size_t)6 * np + 32 + 2);       // ridge_kernel's coef, prev, lam[3], tmp, red (+ alignment)
+    const bool in_lds = plan.in_lds;
+    const size_t lds = plan.bytes;
+    if (!plan.fits) { set_error("bdrt_ridge: n = %d too large", n); return -2; }
     // inputs: a fresh buffer each, filled from the host; outputs and work space: allocated only
     DevBuf<double> dG, dqbase, dfb, dbase, dLs, dlo, dlam0, dlam0s, dbetas, dx0, dPwork, dMwork, dcoef, dlam, dcost, dfun, dhc, dhl, dhf, dhk;
     DevBuf<int> dgsel, diters, dflags;
@@ -798,6 +878,63 @@ int bdrt_ridge(const bdrt_ridge_options *opt, int nb, int ng, const double *G, c
     std::vector<double> fb((size_t)nb, opt->hl_fbeta);
     return bdrt_ridge_ex(opt, zd.data(), fb.data(), nb, ng, G, qbase, gsel, base, Ls, lo, lambda0, lam0s, betas, x0, coef, lam, cost,
                          fun, iters, flags, hist_coef, hist_lam, hist_fun, hist_cost);
+}
+
+int bdrt_debug_qp_factor_solve(const double *P, const double *dg, int n, int nb, int place, const double *rhs, int nrhs,
+                               bdrt_qp_factor_record *rec, double *L_out, double *piv_out, double *sol_out)
+{
+    if (!P || !dg || n < 1 || nb < 1 || (place != 0 && place != 1) || nrhs < 0 || (nrhs > 0 && (!rhs || !sol_out)) || !rec) {
+        set_error("bdrt_debug_qp_factor_solve: bad arguments");
+        return -1;
+    }
+    bind_process_device();
+    const size_t msize = (size_t)n * (n + 1) / 2, nn = (size_t)n * n;
+    const QpLds plan = qp_lds_plan(n, 0);
+    if (!plan.fits || (place == 0 && !plan.in_lds)) {
+        set_error("bdrt_debug_qp_factor_solve: the triangle of n = %d does not fit in LDS", n);
+        return -2;
+    }
+    const bool in_lds = place == 0;
+    const size_t lds = in_lds ? plan.bytes : plan.bytes - (plan.in_lds ? msize * sizeof(double) : 0);
+    DevBuf<double> dP, ddg, drhs, dwork, dreg, dL, dpiv, dsol;
+    DevBuf<int> dok, drungs;
+    if (upload(dP, P, (size_t)nb * nn) || upload(ddg, dg, (size_t)nb * n) || (nrhs > 0 && upload(drhs, rhs, (size_t)nb * nrhs * n))) return -10;
+    if (!in_lds) BDRT_HIP(dwork.alloc((size_t)nb * msize));
+    BDRT_HIP(dok.alloc((size_t)nb));
+    BDRT_HIP(drungs.alloc((size_t)nb));
+    BDRT_HIP(dreg.alloc((size_t)nb));
+    BDRT_HIP(dL.alloc((size_t)nb * nn));
+    BDRT_HIP(dpiv.alloc((size_t)nb * n));
+    if (nrhs > 0) BDRT_HIP(dsol.alloc((size_t)nb * nrhs * n));
+    static LdsAttrCache attr_cache;
+    BDRT_HIP(attr_cache.ensure(lds, [&]() {
+        hipError_t e = hipFuncSetAttribute((const void *)qp_factor_solve_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void *)qp_factor_solve_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        return e;
+    }));
+    if (in_lds)
+        hipLaunchKernelGGL(qp_factor_solve_kernel<true>, dim3(nb), dim3(QP_NT), lds, 0, dP.p, ddg.p, n, drhs.p, nrhs, dwork.p, dok.p, drungs.p,
+                           dreg.p, dL.p, dpiv.p, dsol.p);
+    else
+        hipLaunchKernelGGL(qp_factor_solve_kernel<false>, dim3(nb), dim3(QP_NT), lds, 0, dP.p, ddg.p, n, drhs.p, nrhs, dwork.p, dok.p, drungs.p,
+                           dreg.p, dL.p, dpiv.p, dsol.p);
+    BDRT_HIP(hipGetLastError());
+    BDRT_HIP(hipDeviceSynchronize());
+    std::vector<int> ok(nb), rungs(nb);
+    std::vector<double> reg(nb);
+    if (download(ok.data(), dok.p, (size_t)nb) || download(rungs.data(), drungs.p, (size_t)nb) || download(reg.data(), dreg.p, (size_t)nb)) return -10;
+    int bad = -1;
+    for (int b = 0; b < nb; ++b) {
+        rec[b].ok = ok[b]; rec[b].rungs = rungs[b]; rec[b].reg = reg[b];
+        if (!ok[b]) { if (bad < 0) bad = b; continue; }             // (the caller's arrays of this problem stay as they are)
+        if ((L_out && download(L_out + (size_t)b * nn, dL.p + (size_t)b * nn, nn)) ||
+            (piv_out && download(piv_out + (size_t)b * n, dpiv.p + (size_t)b * n, (size_t)n)) ||
+            (nrhs > 0 && download(sol_out + (size_t)b * nrhs * n, dsol.p + (size_t)b * nrhs * n, (size_t)nrhs * n)))
+            return -10;
+    }
+    if (bad >= 0) { set_error("bdrt_debug_qp_factor_solve: KKT matrix of problem %d not positive definite", bad); return -3; }
+    return 0;
 }
 
 }  // extern "C"

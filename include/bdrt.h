@@ -460,6 +460,24 @@ typedef struct {
 int bdrt_debug_newton_accept(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t,
                              const double *gt, const double *tz, const double *held, double floor_x, int o_x, int Kx);
 
+/* One launch of the box-QP solver's linear algebra on supplied data (no problem handle; the current device), one 512-thread
+ * workgroup per problem: the device code of bdrt_qp_box_batch / bdrt_ridge forms M = (P + P^T) / 2 + diag(dg) + reg I as a packed
+ * lower triangle and factors it, reg = 0 first and then 1e-14 (1 + |M(0,0)|), x 100 per rung while reg <= 1e6, until a Cholesky
+ * factorisation runs to completion; then both substitutions once per right-hand side on that factor.
+ * P [nb][n][n] row-major, not necessarily symmetric; dg [nb][n] (the role of z / s); rhs [nb][nrhs][n] (nrhs may be 0).
+ * place = 0: the triangle in LDS (returns -2 without launching when it does not fit: n > 185); 1: in a global work buffer.
+ * Outputs per problem: rec [nb]; L_out [nb][n][n], the factor as a dense lower triangle with its diagonal (zeros above);
+ * piv_out [nb][n], the pivots the factorisation met (L(j,j)^2 up to the rounding of the square root); sol_out [nb][nrhs][n].
+ * L_out and piv_out may be NULL.  A problem that no rung factors has ok = 0 and leaves its part of L_out, piv_out and sol_out
+ * as the caller passed it; the call then returns -3, as bdrt_qp_box_batch does. */
+typedef struct {
+    int ok;                 /* a rung factored */
+    int rungs;              /* factorisations tried: 1 when reg = 0 sufficed */
+    double reg;             /* the reg added last (ok = 0: the first value beyond 1e6, or NaN) */
+} bdrt_qp_factor_record;
+int bdrt_debug_qp_factor_solve(const double *P, const double *dg, int n, int nb, int place, const double *rhs, int nrhs,
+                               bdrt_qp_factor_record *rec, double *L_out, double *piv_out, double *sol_out);
+
 #ifdef __cplusplus
 }
 #endif
