@@ -100,6 +100,7 @@ SYMBOLS = [
     'bdrt_last_error', 'bdrt_device_count', 'bdrt_set_device', 'bdrt_version',
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
     'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept', 'bdrt_debug_qp_factor_solve',
+    'bdrt_heldout_transformed', 'bdrt_heldout_reduce', 'bdrt_sampler_heldout',
 ]
 
 
@@ -228,6 +229,10 @@ def load_library():
     lib.bdrt_sampler_loo_predict.argtypes = loo_front + [vp] * 9
     lib.bdrt_sampler_loo_group_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bdrt_sampler_loo_group_bytes.restype = C.c_size_t
+    lib.bdrt_heldout_transformed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.bdrt_heldout_reduce.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    # (sampler, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, chunk_bytes, freq_test, H, A_test, z_test), then the outputs
+    lib.bdrt_sampler_heldout.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp] + [vp] * 4
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

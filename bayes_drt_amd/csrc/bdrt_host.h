@@ -239,6 +239,21 @@ int loo_of_draws(const LooDraws &j, double *lpd, double *elpd_loo, double *paret
 int loo_predict_of_draws(const LooDraws &j, double *mean, double *sd, double *pit, double *mean_post, double *sd_post,
                          double *pit_post, double *pareto_k, int *n_tail, double *reff_out);
 
+// Prediction at held-out frequencies and its equal-weight reduction (bdrt_heldout.hip).  The device-pointer cores enqueue on
+// `stream` and return.  dPar [B][D] constrained parameters, dW [H] = 2 pi f, dA per block [2H][K_b] (real rows, then imaginary
+// rows), block after block -> dZh, dSg [B][2H]; -2 for an outlier error model or a grid beyond the LDS of a CU
+int heldout_transformed_device(const char *who, Problem &P, const double *dPar, size_t B, const double *dW, const double *dA, int H,
+                               double *dZh, double *dSg, hipStream_t stream);
+// dTm, dTs [G][N2][S] (transposed Z_hat, sigma_tot), dz [G][N2] -> dOut: 3 planes of G N2 (mean, sd, pit), then lpd [G U]
+int heldout_reduce_device(const double *dTm, const double *dTs, const double *dz, int G, int S, int N2, int pair, double *dOut,
+                          hipStream_t stream);
+// -1 and the error text (in the name of `who`) unless the H held-out frequencies are positive finite numbers
+int heldout_check_grid(const char *who, const double *freq, int H);
+// both on a sampler's draws in chunks of groups: j as for loo_of_draws with pair, col0, ncols counted in the 2H held-out columns
+// (reff_* unused); freq [H], A (as dA) and z_test [G][2H] on the host; outputs on the host, lpd [G][U], the others [G][ncols]
+int heldout_of_draws(const LooDraws &j, const double *freq, int H, const double *A, const double *z_test, double *lpd, double *mean,
+                     double *sd, double *pit);
+
 // rank-normalised diagnostics (bdrt_rank.hip) of the same layout of DEVICE draws, on the split chains; outputs [G x C] on the host
 int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M,
                              int N, int C, double p_lo, double p_hi, double *rhat, double *ess_bulk, double *ess_tail,

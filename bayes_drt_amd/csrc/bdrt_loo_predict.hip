@@ -32,52 +32,6 @@
 namespace bdrt {
 
 constexpr int LP_STAGE = (((LO_MAX_S + 4) / 5) + LO_NT - 1) / LO_NT;         // tail values a thread holds in step 5: 7
-constexpr int LP_NSUM = 7;                       // denominator + 3 terms x 2 scalars
-constexpr int LP_RED = LP_NSUM * LO_NW;          // doubles of reduction scratch
-
-struct PredictArgs {
-    const double *Tm, *Ts;                       // [G][N2][S] device: Z_hat and sigma_tot, transposed
-    const double *z;                             // [G][N2] device
-    const int *M;                                // [units] tail length
-    int S, cap, N2, U, pair;                     // cap = ceil(S / 5); U units per fit = pair ? N2 / 2 : N2
-    double c0, log_dbl_min;
-    double *out;                                 // 6 planes [G][N2]: mean, sd, pit, mean_post, sd_post, pit_post
-    double *khat;                                // [units]
-    int *ntail;
-};
-
-// K sums at once in the order of block_sum: wave butterflies, then the wave partials from wave 0 upward.  red: K * LO_NW doubles
-template <int K>
-__device__ inline void block_sums(double (&v)[K], double *red)
-{
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[k * LO_NW + (threadIdx.x >> 6)] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = waves_sum<LO_NW>(red + k * LO_NW, 1);
-}
-
-// the three terms of one draw and scalar: d = mu - z (centred on the datum: no cancellation), sigma^2 + d^2, Phi((z - mu) / sigma)
-__device__ inline void predict_terms(double mu, double sg, double z, double &d, double &e2, double &phi)
-{
-    d = mu - z;
-    e2 = sg * sg + d * d;
-    phi = 0.5 * erfc(d / (sg * M_SQRT2));
-}
-
-// mean, sd and pit of one scalar from the normalised sums m1 = E d, m2 = E (sigma^2 + d^2), p = E Phi
-__device__ inline void predict_write(double *out, size_t plane, size_t e, double z, double m1, double m2, double p)
-{
-    out[e] = z + m1;
-    out[plane + e] = sqrt(m2 - m1 * m1);
-    out[2 * plane + e] = p;
-}
-
 __global__ __launch_bounds__(LO_NT) void predict_kernel(PredictArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];

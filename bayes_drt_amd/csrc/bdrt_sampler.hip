@@ -750,16 +750,18 @@ int bdrt_sampler_rank_diagnostics(bdrt_sampler *s, int unit_lo, int unit_hi, int
 }
 
 // Common front of bdrt_sampler_loo and bdrt_sampler_loo_predict: argument checks, sampler_draws, and the job for the device
-// reductions (bdrt_host.h).  name: the entry point; spec: storage for the groups' spectra.
+// reductions (bdrt_host.h).  name: the entry point; spec: storage for the groups' spectra; n2: the scalar columns a group has
+// (0: the 2 Nf of the problem's grid; bdrt_sampler_heldout: the 2 H of the held-out grid).
 static int sampler_loo_job(const char *name, bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0,
-                           int ncols, int reff_mode, const double *reff_in, size_t chunk_bytes, std::vector<int> &spec, LooDraws &j)
+                           int ncols, int reff_mode, const double *reff_in, size_t chunk_bytes, std::vector<int> &spec, LooDraws &j,
+                           int n2 = 0)
 {
     if (!s || chains_per_group < 1 || (pair != 0 && pair != 1) || reff_mode < 0 || reff_mode > 2 || (reff_mode == 1 && !reff_in)) {
         set_error("%s: bad arguments", name);
         return -1;
     }
     Sampler &S = s->impl;
-    const int N2 = 2 * S.prob->dev.nf;
+    const int N2 = n2 > 0 ? n2 : 2 * S.prob->dev.nf;
     if (col0 < 0 || ncols < 1 || col0 + ncols > N2 || (pair && (col0 != 0 || ncols != N2))) {
         set_error("%s: bad column range (pair = 1 needs all %d columns)", name, N2);
         return -1;
@@ -815,6 +817,27 @@ int bdrt_sampler_loo_predict(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
                                  reff_in, chunk_bytes, spec, j))
         return rc;
     return loo_predict_of_draws(j, mean, sd, pit, mean_post, sd_post, pit_post, pareto_k, n_tail, reff_out);
+}
+
+int bdrt_sampler_heldout(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                         size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, double *lpd,
+                         double *mean, double *sd, double *pit)
+{
+    if (!freq_test || !A_test || !z_test || !lpd || !mean || !sd || !pit || H < 1) {
+        set_error("bdrt_sampler_heldout: bad arguments");
+        return -1;
+    }
+    if (s && s->impl.prob->dev.outlier_mode) {
+        set_error("bdrt_sampler_heldout: outlier error models are refused: a held-out point has no sigma_out of its own");
+        return -2;
+    }
+    if (heldout_check_grid("bdrt_sampler_heldout", freq_test, H)) return -1;
+    std::vector<int> spec;
+    LooDraws j;
+    if (int rc = sampler_loo_job("bdrt_sampler_heldout", s, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, 0, nullptr, chunk_bytes,
+                                 spec, j, 2 * H))
+        return rc;
+    return heldout_of_draws(j, freq_test, H, A_test, z_test, lpd, mean, sd, pit);
 }
 
 size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict)

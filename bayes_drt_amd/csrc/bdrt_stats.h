@@ -1,5 +1,5 @@
 // bdrt_stats.h -- device pieces shared by the post-sampling statistics: bdrt_post.hip, bdrt_diag.hip, bdrt_rank.hip, bdrt_loo.hip,
-// bdrt_loo_predict.hip (the last two through bdrt_psis.h).
+// bdrt_loo_predict.hip, bdrt_heldout.hip (the last three through bdrt_psis.h).
 //
 // Every includer is compiled with -ffp-contract=off (Makefile): the products that accumulate are explicit fma() calls, everything
 // else is rounded separately, as in the numpy statements these kernels are held to (tests/diag_numpy.py, rank_numpy.py,

@@ -410,9 +410,9 @@ class StanModel:
         return res
 
     def sampling(self, data, warmup=200, iter=400, chains=2, seed=1234, init='random', control=None,
-                 chain_ids=None, rounds_per_launch=None, loo=None):
-        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan.  loo: `sample_units`' argument; what it
-        reduces is the fit's `device_loo`."""
+                 chain_ids=None, rounds_per_launch=None, loo=None, heldout=None):
+        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan.  loo, heldout: `sample_units`'
+        arguments; what they reduce is the fit's `device_loo` / `device_heldout`."""
         P = self._prepare(data)
         n_draws = int(iter) - int(warmup)
         if n_draws < 0:
@@ -425,13 +425,15 @@ class StanModel:
         if not (init is None or (isinstance(init, str) and init == 'random')):
             init_theta = self._init_theta(init, chains, seed)
         res = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
-                           chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo)
+                           chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo, heldout=heldout)
         draws, lp, diag = res[:3]
         theta = draws.reshape(chains * n_draws, P.D)
         fit = StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
                       control=dict(adapt_delta=ctrl.adapt_delta, max_treedepth=ctrl.max_treedepth), warmup=warmup)
         if loo is not None:
             fit.device_loo = res[3]
+        if heldout is not None:
+            fit.device_heldout = res[-1]
         return fit
 
 
@@ -560,6 +562,13 @@ class Sampler:
         from .loo import sampler_psis_predict
         return sampler_psis_predict(self, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes)
 
+    def heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both', chunk_bytes=None):
+        """What the draws of the same groups predict at frequencies that are not on the problem's grid, against the held-out
+        data z_test [groups, 2 H], reduced where the draws are (bdrt_sampler_heldout): `loo.heldout_reduce`'s dict.
+        Arguments: `loo.sampler_heldout`."""
+        from .loo import sampler_heldout
+        return sampler_heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit, part, chunk_bytes)
+
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""
         p = self._lib.bdrt_sampler_draws_dev(self.handle)
@@ -578,14 +587,27 @@ class Sampler:
 
 
 def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, chain_ids=None, init_theta=None,
-                 rounds_per_launch=None, diagnostics_chains=None, loo=None):
+                 rounds_per_launch=None, diagnostics_chains=None, loo=None, heldout=None):
     """Run n_units chains (unit u: spectrum spec[u], RNG stream (seed, chain_ids[u])) to completion on the GPU.
     Returns draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain diagnostics.
     diagnostics_chains=M: also reduce the convergence diagnostics of the constrained parameters, groups of M consecutive units,
     in one launch while the sampler still holds the draws; a fourth item (mean, sd, n_eff, Rhat), each [n_units / M, D].
     loo=dict(chains=M, loo=True, predict=False, unit=, part=, reff=, chunk_bytes=): also reduce PSIS-LOO (`Sampler.loo`) and / or
     the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; one more item, a dict
-    with the entries 'loo' and / or 'predict'."""
+    with the entries 'loo' and / or 'predict'.
+    heldout=dict(chains=M, freq_test=, A_test_blocks=, z_test=, unit=, part=, chunk_bytes=): also reduce the predictive of held-out
+    frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; one more item (the last), its dict."""
+    hkw = None
+    if heldout is not None:
+        hkw = dict(heldout)
+        need = {'chains', 'freq_test', 'A_test_blocks', 'z_test'}
+        unknown = sorted(set(hkw) - need - {'unit', 'part', 'chunk_bytes'})
+        if unknown or not need <= set(hkw):
+            raise ValueError('sample_units: heldout needs chains, freq_test, A_test_blocks, z_test and takes unit, part, chunk_bytes '
+                             '(got %s)' % sorted(hkw))
+        from .loo import _heldout_grid, _heldout_part
+        f_, _ = _heldout_grid(problem, hkw['freq_test'], hkw['A_test_blocks'], 'heldout')
+        _heldout_part(hkw.get('unit', 'frequency'), hkw.get('part', 'both'), len(f_), 'heldout')
     kw = None
     if loo is not None:
         kw = dict(loo)
@@ -608,6 +630,9 @@ def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, 
             if kw.get('predict', False):
                 out['predict'] = smp.loo_predict(*args)
             res = res + (out,)
+        if hkw is not None:
+            res = res + (smp.heldout(0, n_units, hkw['chains'], hkw['freq_test'], hkw['A_test_blocks'], hkw['z_test'],
+                                     hkw.get('unit', 'frequency'), hkw.get('part', 'both'), hkw.get('chunk_bytes')),)
         return res
 
 

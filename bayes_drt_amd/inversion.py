@@ -975,7 +975,7 @@ class Inverter:
             init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
             mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
             model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True,
-            loo=False, loo_predict=False, loo_kw=None):
+            loo=False, loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency'):
         """Fit the distribution(s) with the calibrated hierarchical Bayesian model: mode='optimize' (MAP) or
         'sample' (NUTS).  Arguments as in the reference (:1072-1152), plus two that only concern mode='optimize':
 
@@ -993,9 +993,12 @@ class Inverter:
             divergences, tree depth; n_eff and R-hat skipped above 1000 flat names), logged at WARNING to
             logging.getLogger('bayes_drt_amd') (bayes_drt_amd.diagnostics); False: no check.
         loo, loo_predict, loo_kw : mode='sample' only -- as in `fit_many`: `loo_result` / `loo_predict_result` reduced while
-            the sampler still holds the draws."""
+            the sampler still holds the draws.
+        heldout, heldout_unit : mode='sample' only -- as in `fit_many`: (f_test, Z_test), frequencies this fit does not see;
+            `heldout_result` is what its draws predict there."""
         self._fit_argument_checks(part, mode, fitY, SA, SASY, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
+        hkw = self._heldout_arguments(heldout, heldout_unit, 1, mode, part, [outliers], None)
         job = self._fit_prepare(frequencies, Z, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                 inductance_scale, outlier_lambda, mode, add_stan_data, model_str, fitY, SA, SASY, n_starts)
         model, dat = job['model'], job['dat']
@@ -1004,11 +1007,14 @@ class Inverter:
                                                 extra_inits=job['extra_inits'], algorithm=algorithm or 'LBFGS+Newton')
             self._opt_report = model.last_report
         else:
+            held = None if hkw is None else self._heldout_job([self], [job], hkw, part, chains)
             self._sample_result = model.sampling(dat, warmup=warmup, iter=warmup + samples, chains=chains,
                                                  seed=random_seed, init=job['init'], control=dict(self._NUTS_CONTROL),
-                                                 loo=None if lkw is None else dict(lkw, chains=chains))
+                                                 loo=None if lkw is None else dict(lkw, chains=chains), heldout=held)
             if lkw is not None:
                 self._store_device_loo(self._sample_result.device_loo, 0, lkw, dat, chains * samples)
+            if held is not None:
+                self._store_heldout(self._sample_result.device_heldout, 0, held, chains * samples)
             if check_diagnostics:
                 from . import diagnostics
                 diagnostics.auto_check(self._sample_result, diagnostics.flat_parameter_count(job['model_str'], dat))
@@ -1072,7 +1078,7 @@ class Inverter:
                  init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
                  mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
                  model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True, loo=False,
-                 loo_predict=False, loo_kw=None):
+                 loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency'):
         """The fits `[copy(self).fit(frequencies, Z, ...) for Z in Z_list]` -- the reference's own workload is such a loop
         over spectra measured on one frequency grid (code_EchemActa/Run fits.ipynb cells 4-5, inversion.py:1072-1081,
         :1218-1221) -- as ONE batch: one shared problem in HBM (the matrices are those of the common grid), every
@@ -1097,9 +1103,21 @@ class Inverter:
         draws (`Sampler.loo`, `Sampler.loo_predict`): the draws do not go back to the device, Z_hat, sigma_tot and the log-
         likelihoods never leave it, and inside a process group each rank reduces its own spectra.  loo_kw: dict with `unit` and
         `reff` as in `loo` (default 'frequency', 'auto'); the part is the fit's.  With reff None or a number the results equal
-        `loo_many` on the views bit for bit; reff='auto' is reduced on the device and may differ from the host's in the last bits."""
+        `loo_many` on the views bit for bit; reff='auto' is reduced on the device and may differ from the host's in the last bits.
+        heldout (mode='sample'; ValueError with mode='optimize'): (f_test, Z_test), frequencies the fits do not see and the
+        impedance measured there -- one pair for all spectra, or a list with one pair per spectrum (spectra that share a batch must
+        share f_test).  Every view gets `heldout_result`, a `LooResult` of what its draws predict at f_test (the equal-weight
+        mixture of the draws' normals; `Sampler.heldout`, reduced while the sampler still holds the draws): frequencies, elpd
+        (the sum) and elpd_i per unit, Z_pred (complex), sigma_pred_re/_im, pit_re/_im, resid_re/_im, n_draws, in the units of the
+        impedance as supplied and in the order of f_test.  heldout_unit: 'frequency' or 'point'; with part 'real' / 'imag' the
+        other half is NaN and units are points, as in `loo_predict`.  NotImplementedError for the outlier error models (a held-out
+        point has no sigma_out) and inside a process group with more than one rank."""
         self._fit_argument_checks(part, mode, False, False, False, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
+        hkw = self._heldout_arguments(heldout, heldout_unit, len(Z_list), mode, part,
+                                      self._per_spectrum(outliers, len(Z_list), 'outliers'), group)
+        if hkw is not None:
+            self._heldout_shared_grids(hkw, frequencies, len(Z_list), (nonneg, outliers, sigma_min, inductance_scale, outlier_lambda))
         views, jobs = self._batch_jobs(frequencies, Z_list, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                        inductance_scale, outlier_lambda, mode, add_stan_data, model_str, n_starts)
         if not views:
@@ -1110,9 +1128,18 @@ class Inverter:
         order = {}
         for i, job in enumerate(jobs):
             order.setdefault(self._batch_key(job), []).append(i)
+        if hkw is not None:                                                  # (batches that only `_batch_jobs` could tell: before the first is sampled)
+            for idx in order.values():
+                f0 = hkw['pairs'][idx[0]][0]
+                if any(not np.array_equal(hkw['pairs'][i][0], f0) for i in idx[1:]):
+                    raise ValueError('heldout: the spectra of one batch must share f_test (spectra %s)' % idx)
+                if any(jobs[i]['outliers'] for i in idx):
+                    from . import loo as _loo
+                    raise NotImplementedError('fit_many(heldout=...): ' + _loo.OUTLIER_REFUSAL)
         for idx in order.values():
             self._fit_batch([views[i] for i in idx], [jobs[i] for i in idx], mode, random_seed, max_iter, warmup, samples,
-                            chains, algorithm, group, check_diagnostics, idx, lkw)
+                            chains, algorithm, group, check_diagnostics, idx, lkw,
+                            None if hkw is None else dict(hkw, pairs=[hkw['pairs'][i] for i in idx], part=part))
         for inv, job in zip(views, jobs):
             inv._fit_finish(job, mode, job['sigma_min'], check_outliers)
         return views
@@ -1146,12 +1173,108 @@ class Inverter:
                 p = {k: v[g] for k, v in res['loo'].items()}
                 self.loo_result = _loo._result(p, 2 if pair else 1, S,
                                                float(np.log(self._Z_scale)), freq, prefix)
+                self._loo_unit_part = (lkw['unit'], part)
             if 'predict' in res:
                 p = {k: v[g] for k, v in res['predict'].items()}
                 zc = z if part == 'both' else (z[:nf] if part == 'real' else z[nf:])
                 self.loo_predict_result = self._loo_predict_view(_loo._predict_result(p, zc, S, freq, prefix), part, freq)
         finally:
             _loo.logger.disabled = was
+
+    @staticmethod
+    def _heldout_arguments(heldout, unit, n, mode, part, outliers, group):
+        """`heldout=` of `fit` / `fit_many` -> dict(pairs=[(f_test, Z_test) per spectrum], unit=) (None: not asked for), checked
+        before any GPU work."""
+        if heldout is None:
+            return None
+        from . import loo as _loo
+        if mode != 'sample':
+            raise ValueError("heldout needs the draws of mode='sample'; the predictive of a MAP fit is not defined here")
+        if any(not isinstance(o, str) and bool(o) for o in outliers):            # ('auto' is looked at once it has decided)
+            raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+                raise NotImplementedError('fit_many(heldout=...) is not available inside a process group with more than one rank')
+        except ImportError:
+            pass
+        _loo.check_device_args('point' if part != 'both' else unit, part, None, 'heldout')
+        _loo._pair(unit)
+
+        def is_pair(h):
+            """(f_test, Z_test): two one-dimensional arrays or sequences of numbers"""
+            if not (isinstance(h, (tuple, list)) and len(h) == 2):
+                return False
+            try:
+                a, b = np.asarray(h[0]), np.asarray(h[1])
+            except ValueError:                                               # (ragged: no pair of arrays)
+                return False
+            return a.ndim == 1 and b.ndim == 1 and a.dtype != object and b.dtype != object
+        if is_pair(heldout):
+            pairs = [heldout] * n
+        elif isinstance(heldout, (tuple, list)) and len(heldout) == n and all(is_pair(h) for h in heldout):
+            pairs = list(heldout)
+        else:
+            raise ValueError('heldout must be (f_test, Z_test) or a list with one such pair per spectrum (%d)' % n)
+        out = []
+        for f, Z in pairs:
+            f, Z = np.asarray(f, dtype=float), np.asarray(Z)
+            if len(f) < 1 or len(f) != len(Z):
+                raise ValueError('heldout: f_test and Z_test must have the same length, at least 1')
+            _validate_spectrum(f, Z)
+            out.append((f, Z))
+        return dict(pairs=out, unit='point' if part != 'both' else unit)
+
+    @classmethod
+    def _heldout_shared_grids(cls, hkw, frequencies, n, options):
+        """Spectra that will share a batch -- one training grid, equal per-spectrum options -- must share f_test: refused here,
+        before any matrix is built or any batch sampled.  (Grids that differ in their last bits only, and outliers='auto', are
+        told apart by `_batch_jobs`; `fit_many` looks again behind it.)"""
+        per_grid = (isinstance(frequencies, (list, tuple)) and n > 0 and len(frequencies) == n and
+                    all(np.ndim(f) == 1 for f in frequencies)) or (isinstance(frequencies, np.ndarray) and frequencies.ndim == 2)
+        grids = list(frequencies) if per_grid else [frequencies] * n
+        opts = [cls._per_spectrum(v, n, 'option') for v in options]
+        seen = {}
+        for i in range(n):
+            if any(isinstance(o[i], str) for o in opts):
+                continue
+            key = (np.sort(np.asarray(grids[i], dtype=float))[::-1].tobytes(),) + tuple(repr(o[i]) for o in opts)
+            j = seen.setdefault(key, i)
+            if not np.array_equal(hkw['pairs'][i][0], hkw['pairs'][j][0]):
+                raise ValueError('heldout: the spectra of one batch must share f_test (spectra %d and %d)' % (j, i))
+
+    def _block_distributions(self, model_type):
+        """Names of the distributions in the order of the model's blocks (`engine.blocks_from_dat`)."""
+        d = self.distributions
+        if model_type in ('Series', 'Parallel'):
+            return [[k for k, v in d.items() if v['dist_type'] == model_type.lower()][0]]
+        return [k for k, v in d.items() if v['dist_type'] == 'series'][:1] + sorted(k for k, v in d.items() if v['dist_type'] == 'parallel')
+
+    @staticmethod
+    def _heldout_job(views, jobs, hkw, part, chains):
+        """The `heldout=` dict for the engine: the prediction rows of the batch's common held-out grid from
+        `_get_prediction_matrices`, and the held-out data of every spectrum on that spectrum's own scale (`scale_Z` has seen the
+        training rows only)."""
+        from . import loo as _loo
+        if any(job['outliers'] for job in jobs):
+            raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
+        f0 = hkw['pairs'][0][0]
+        if any(len(f) != len(f0) or not np.array_equal(f, f0) for f, _ in hkw['pairs'][1:]):
+            raise ValueError('heldout: the spectra of one batch must share f_test')
+        keep_re, keep_im = float(part != 'imag'), float(part != 'real')
+        names = views[0]._block_distributions(jobs[0]['model_type'])
+        pm = views[0]._get_prediction_matrices(f0, names)
+        A = [np.concatenate((keep_re * pm[n]['A_re'], keep_im * pm[n]['A_im'])) for n in names]
+        z = np.vstack([np.concatenate((keep_re * Z.real, keep_im * Z.imag)) / inv._Z_scale for inv, (_, Z) in zip(views, hkw['pairs'])])
+        return dict(chains=chains, freq_test=f0, A_test_blocks=A, z_test=z, unit=hkw['unit'], part=part)
+
+    def _store_heldout(self, res, g, held, S):
+        """Row g of `Sampler.heldout`'s dict -> `heldout_result`."""
+        from . import loo as _loo
+        H, part = len(held['freq_test']), held['part']
+        cols = {'both': slice(0, 2 * H), 'real': slice(0, H), 'imag': slice(H, 2 * H)}[part]
+        self.heldout_result = _loo.heldout_result({k: v[g] for k, v in res.items()}, held['z_test'][g][cols], held['freq_test'], part,
+                                                  held['unit'], S, self._Z_scale)
 
     @staticmethod
     def _batch_key(job):
@@ -1237,9 +1360,9 @@ class Inverter:
 
     @staticmethod
     def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics=False,
-                   index=None, lkw=None):
-        """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view, and with `lkw`
-        (`_loo_arguments`) `loo_result` / `loo_predict_result`."""
+                   index=None, lkw=None, hkw=None):
+        """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view, with `lkw`
+        (`_loo_arguments`) `loo_result` / `loo_predict_result`, and with `hkw` (`_heldout_arguments`) `heldout_result`."""
         import ctypes as C
         from . import engine, parallel
         from ._lib import NutsControl
@@ -1311,6 +1434,7 @@ class Inverter:
         from . import diagnostics
         flat = diagnostics.flat_parameter_count(jobs[0]['model_str'], dat)
         param_stats = None
+        held = None if hkw is None else Inverter._heldout_job(views, jobs, hkw, hkw['part'], chains)
         if world > 1:
             blocks, kw, _ = engine.blocks_from_dat(model.model_name, dat)
             pk = dict(kw, blocks=blocks, Z=np.asarray(dat['Z'], dtype=float), freq=np.asarray(dat['freq'], dtype=float))
@@ -1332,7 +1456,9 @@ class Inverter:
             want = chains if (check_diagnostics and flat <= diagnostics.MAX_FLAT) else None
             res = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
                                       init_theta=init_theta, diagnostics_chains=want,
-                                      loo=None if lkw is None else dict(lkw, chains=chains))
+                                      loo=None if lkw is None else dict(lkw, chains=chains), heldout=held)
+            if held is not None:
+                res, held_res = res[:-1], res[-1]
             draws, lp, diag = res[:3]
             if want:
                 param_stats = res[3]
@@ -1346,6 +1472,8 @@ class Inverter:
                 # (with several ranks every rank holds the same results and only rank 0 logs)
                 inv._store_device_loo(loo_res, i, lkw, dat, chains * n_draws, i if index is None else index[i],
                                       quiet=world > 1 and dist.get_rank(group) != 0)
+            if held is not None:
+                inv._store_heldout(held_res, i, held, chains * n_draws)
         # with several ranks only rank 0 runs the check (and logs): every rank holds the same results
         if check_diagnostics and (world == 1 or dist.get_rank(group) == 0):
             diagnostics.batch_check([inv._sample_result for inv in views], flat, param_stats, index)
@@ -1850,6 +1978,7 @@ class Inverter:
         fit, z, columns, freq = self._loo_job(part)
         self.loo_result = _loo.loo(fit, z, unit=unit, reff=reff, log_scale=float(np.log(self._Z_scale)), columns=columns,
                                    frequencies=freq)
+        self._loo_unit_part = ('point' if part != 'both' else unit, part)        # (what `reloo` asks of the result it repairs)
         return self.loo_result
 
     @staticmethod
@@ -1867,6 +1996,7 @@ class Inverter:
                             chunk_bytes=chunk_bytes or _loo.CHUNK_BYTES)
         for inv, r in zip(inverters, res):
             inv.loo_result = r
+            inv._loo_unit_part = ('point' if part != 'both' else unit, part)
         return res
 
     def _loo_predict_view(self, r, part, freq):
@@ -1935,6 +2065,131 @@ class Inverter:
         with np.errstate(invalid='ignore'):
             zs = np.sqrt((r['resid_re'] ** 2 + r['resid_im'] ** 2) / 2)
             return np.argwhere(zs > threshold)
+
+    # ================================================================== K-fold and exact refits (bayes_drt_amd.loo)
+    def _pinned_copy(self, frequencies):
+        """A copy of this instance whose basis is that of the full grid `frequencies` whatever rows a refit drops: `basis_freq` of
+        every distribution is pinned (with it tau, K and epsilon), so that every fold fits the same model and only the data rows
+        shrink.  The copy has a matrix cache of its own."""
+        import copy
+        f = np.asarray(frequencies, dtype=float)
+        inv = copy.copy(self)
+        inv.distribution_matrices = {}
+        dists = deepcopy(self.distributions)
+        for info in dists.values():
+            if info.get('basis_freq', self.basis_freq) is None:
+                tmin = np.log10(1 / (2 * np.pi * np.max(f))) - 1             # (the rule of `_prep_matrices`)
+                tmax = np.log10(1 / (2 * np.pi * np.min(f))) + 1
+                info['basis_freq'] = 1 / (2 * np.pi * np.logspace(tmin, tmax, int(10 * (tmax - tmin) + 1)))
+            elif 'basis_freq' not in info:
+                info['basis_freq'] = np.array(self.basis_freq, dtype=float)
+            info.pop('tau', None)
+            if info.get('epsilon', self.epsilon) is None:
+                info.pop('epsilon', None)
+        inv.distributions = dists
+        inv._cached_distributions = {}
+        inv.__dict__.update(f_train=[0], Z_train=None, f_pred=None)
+        return inv
+
+    @staticmethod
+    def _refit_kw(fit_kw, who):
+        kw = dict(fit_kw)
+        if kw.setdefault('mode', 'sample') != 'sample':
+            raise ValueError("%s needs mode='sample': the folds are sampling fits" % who)
+        for k in ('heldout', 'heldout_unit', 'group'):
+            if k in kw:
+                raise ValueError('%s: %s is set by %s itself' % (who, k, who))
+        if any(not isinstance(o, str) and bool(o) for o in np.atleast_1d(np.asarray(kw.get('outliers', False), dtype=object))):
+            from . import loo as _loo
+            raise NotImplementedError('%s: %s' % (who, _loo.OUTLIER_REFUSAL))
+        kw.setdefault('check_outliers', False)
+        return kw
+
+    def kfold_many(self, frequencies, Z_list, folds=10, unit='frequency', **fit_kw):
+        """K-fold cross-validation of many spectra on ONE grid: for each fold one `fit_many` batch of all spectra on the
+        training rows with `heldout=` the fold's rows -- `folds` engine calls, not folds x spectra --, reduced on the GPU while
+        the sampler holds the draws.  Fold assignment has no random numbers (`loo.fold_labels`): the frequencies sorted in
+        descending order, sorted index i in fold i % folds, so every fold spans the whole range; or `folds` is an integer array,
+        one fold label per frequency in the order given.  Every fold fits the same model: the basis is pinned to that of the full
+        grid and only the data rows shrink; every fold has its own Z scale, as `scale_Z` looks at the training rows only.
+        fit_kw: arguments of `fit_many` (mode='sample' is implied; outlier error models raise NotImplementedError).
+        Returns a list of Inverter objects (shallow copies of this one, without fit attributes of their own), one per spectrum,
+        each with `kfold_result`: a `LooResult` that `loo.compare` ranks -- elpd_loo (the sum of the folds' elpd_i), se, elpd_i
+        in the order of the supplied grid, n_units; p_loo NaN, pareto_k all NaN, n_bad_k 0 -- with method='kfold', the `fold` of
+        every unit and the predictive arrays of `heldout_result`.  The fold fits are not kept; this instance is left as it was."""
+        import copy
+        from . import loo as _loo
+        f = np.asarray(frequencies, dtype=float)
+        if f.ndim != 1:
+            raise ValueError('kfold_many: one frequency grid for all spectra')
+        Z_list = [np.asarray(Z) for Z in Z_list]
+        for Z in Z_list:
+            _validate_spectrum(f, Z)
+        labels = _loo.fold_labels(f, folds)
+        kw = self._refit_kw(fit_kw, 'kfold')
+        part = kw.get('part', 'both')
+        hunit = 'point' if part != 'both' else unit
+        _loo.check_device_args(hunit, part, None, 'kfold')
+        if not Z_list:
+            return []
+        base = self._pinned_copy(f)
+        per_fold = [dict() for _ in Z_list]
+        log = _loo.logger.getChild('kfold')
+        for lab in np.unique(labels).tolist():
+            test = labels == lab
+            views = base.fit_many(f[~test], [Z[~test] for Z in Z_list], heldout=[(f[test], Z[test]) for Z in Z_list],
+                                  heldout_unit=unit, **kw)
+            log.info('kfold: fold %s done: %d spectra fitted on %d frequencies, %d held out', lab, len(views), int(np.sum(~test)),
+                     int(np.sum(test)))
+            for i, v in enumerate(views):
+                per_fold[i][lab] = v.heldout_result
+        out = []
+        for i in range(len(Z_list)):
+            inv = copy.copy(self)
+            inv.kfold_result = _loo.kfold_result(labels, per_fold[i], hunit, part)
+            out.append(inv)
+        return out
+
+    def kfold(self, frequencies, Z, folds=10, unit='frequency', **fit_kw):
+        """`kfold_many` of one spectrum: stores the result as `kfold_result` of THIS instance and returns it."""
+        self.kfold_result = self.kfold_many(frequencies, [Z], folds=folds, unit=unit, **fit_kw)[0].kfold_result
+        return self.kfold_result
+
+    def reloo(self, frequencies, Z, k_threshold=0.7, max_refits=8, **fit_kw):
+        """Exact leave-one-out for the frequencies PSIS flags: for every unit of this instance's `loo_result` with
+        pareto_k > k_threshold one refit without that frequency (`fit(..., heldout=...)` on a copy whose basis is pinned to the
+        full grid), whose `heldout_result` replaces the unit's elpd_i.  Every refit has its own grid, so they run one after the
+        other: THIS COSTS ONE `fit` PER FLAGGED FREQUENCY; with more than max_refits of them a ValueError names `kfold` as the
+        cheaper route (max_refits=None lifts the cap).  Needs `loo_result` from `loo(unit='frequency', part='both')` (or
+        `fit(..., loo=True)`) of a fit of (frequencies, Z); fit_kw: the arguments that fit was run with (mode='sample' is implied).
+        elpd_loo, se, p_loo (the sum of lpd_i - elpd_i) and n_bad_k (units still above 0.7 and not refit) are recomputed; lpd_i,
+        pareto_k, the WAIC entries and every untouched elpd_i keep their bits; `refit` [n_units] marks the replaced units and
+        method is 'psis+refit'.  Stores and returns the new `loo_result`."""
+        from . import loo as _loo
+        r = getattr(self, 'loo_result', None)
+        f, Z = np.asarray(frequencies, dtype=float), np.asarray(Z)
+        _validate_spectrum(f, Z)
+        if r is None or 'lpd_i' not in r or int(r['n_units']) != len(f) or \
+                getattr(self, '_loo_unit_part', None) != ('frequency', 'both'):
+            raise ValueError("reloo needs this instance's loo_result per frequency of the supplied grid: call "
+                             "loo(unit='frequency', part='both') (or fit(..., loo=True)) first")
+        kw = self._refit_kw(fit_kw, 'reloo')
+        if kw.get('part', 'both') != 'both':
+            raise ValueError("reloo needs unit='frequency', part='both': call loo(unit='frequency', part='both') first")
+        cand = _loo.reloo_candidates(r, k_threshold, max_refits)
+        order = np.argsort(f)[::-1]                                  # the order of the fit's rows, hence of loo_result's units
+        f, Z = f[order], Z[order]
+        exact = {}
+        if len(cand):
+            base = self._pinned_copy(f)
+            for i in cand.tolist():
+                keep = np.arange(len(f)) != i
+                v = base.fit_many(f[keep], [Z[keep]], heldout=(f[~keep], Z[~keep]), **kw)[0]
+                exact[i] = float(v.heldout_result['elpd_i'][0])
+                _loo.logger.getChild('reloo').info('reloo: refit %d of %d without f = %.4g Hz: elpd_i %.3f (PSIS %.3f, k %.2f)',
+                                                              len(exact), len(cand), f[i], exact[i], r['elpd_i'][i], r['pareto_k'][i])
+        self.loo_result = _loo.reloo_result(r, exact)
+        return self.loo_result
 
     # ================================================================== prediction (reference :2571-3311)
     def _get_prediction_matrices(self, frequencies, distributions):

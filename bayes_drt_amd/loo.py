@@ -28,8 +28,15 @@ downloaded draws bit for bit (`host_psis_loo`, `host_psis_predict` are that path
 device too (exp(ll - max ll) per observation, then the kernel of `column_diagnostics`), and since the device's exp is not numpy's,
 the relative efficiency may differ from `relative_efficiency` in its last bits: the result carries the 'reff' that was used.
 
-Out of scope: K-fold or exact refits and moment matching for high-k observations; LOO of MAP or ridge fits; predictive checks
-with replicated data, plots, and a `fit_many` that keeps no draws at all.
+Held-out frequencies (`heldout_transformed`, `heldout_reduce`; `sampler_heldout`, `host_heldout`; `Sampler.heldout`): what the
+draws of a fit on a training grid predict at frequencies that are not on it -- Z_hat and sigma_tot of every draw there
+(bdrt_heldout.hip), then the equal-weight mixture of the draws' normals: lpd, mean, sd and PIT per held-out unit.  This is the
+exact remedy for observations PSIS flags: `Inverter.reloo` refits without each of them, `Inverter.kfold_many` runs K folds of
+many spectra as K batches; both give `LooResult`s that `compare` ranks.  Definitions: tests/heldout_numpy.py.  Outlier error
+models are refused: every training point has its own sigma_out and a held-out point has none.
+
+Out of scope: moment matching for high-k observations; held-out prediction for outlier error models; stacking weights; LOO of
+MAP or ridge fits; predictive checks with replicated data, plots, and a `fit_many` that keeps no draws at all.
 """
 import logging
 
@@ -260,6 +267,146 @@ def sampler_psis_predict(sampler, unit_lo, unit_hi, chains, unit='frequency', pa
     return dict(zip(PREDICT_FIELDS, outs), pareto_k=k, n_tail=n_tail, reff=used)
 
 
+# ---------------------------------------------------------------------------------------------------- held-out frequencies
+HELDOUT_FIELDS = ('mean', 'sd', 'pit')
+OUTLIER_REFUSAL = ('held-out prediction is not defined for the outlier error models (*_outliers): every training point has its '
+                   'own sigma_out and a held-out point has none')
+
+
+def _heldout_grid(problem, freq_test, A_test_blocks, who):
+    """Checks of the held-out grid that need no GPU -> (freq [H], the prediction rows packed as bdrt_heldout_transformed takes
+    them).  A_test_blocks: per block of the problem (A_re, A_im), each [H, K_b], or the two stacked, [2 H, K_b]."""
+    if int(getattr(getattr(problem, 'dat', None), 'outlier_mode', 0)):
+        raise NotImplementedError('%s: %s' % (who, OUTLIER_REFUSAL))
+    freq = np.ascontiguousarray(np.asarray(freq_test, dtype=float).reshape(-1))
+    H = len(freq)
+    if H < 1 or not np.all(np.isfinite(freq) & (freq > 0)):
+        raise ValueError('%s: freq_test must hold at least one positive finite frequency' % who)
+    Ks = list(problem.Ks)
+    if len(A_test_blocks) != len(Ks):
+        raise ValueError('%s: %d blocks of prediction rows for a problem of %d blocks' % (who, len(A_test_blocks), len(Ks)))
+    parts = []
+    for b, (A, K) in enumerate(zip(A_test_blocks, Ks)):
+        if isinstance(A, (tuple, list)):
+            if len(A) != 2:
+                raise ValueError('%s: block %d: (A_re, A_im) expected' % (who, b))
+            A = np.concatenate([np.atleast_2d(np.asarray(a, dtype=float)) for a in A])
+        A = np.asarray(A, dtype=float)
+        if A.shape != (2 * H, K):
+            raise ValueError('%s: block %d: prediction rows %s, expected (%d, %d): real rows, then imaginary rows'
+                             % (who, b, A.shape, 2 * H, K))
+        parts.append(A.reshape(-1))
+    return freq, np.ascontiguousarray(np.concatenate(parts))
+
+
+def _heldout_draw_count(S, who):
+    if S < 2:
+        raise ValueError('%s: at least 2 draws are needed' % who)
+    if S > max_draws():
+        raise ValueError('%s: %d draws per unit, the kernel holds at most %d' % (who, S, max_draws()))
+
+
+def heldout_transformed(problem, params, freq_test, A_test_blocks):
+    """Z_hat and sigma_tot [B, 2 H] (real halves, then imaginary halves) of B rows of CONSTRAINED parameters -- params [B, D]
+    as `Problem.transformed` returns them -- at the frequencies freq_test [H], which need not be on the problem's grid, on the
+    GPU (bdrt_heldout_transformed).  A_test_blocks: the prediction rows, per block (A_re, A_im) [H, K_b] each or stacked
+    [2 H, K_b].  Block flags, x_scale, induc_scale and sigma_min are the problem's.  A row's result does not depend on what
+    else is in the call.  NotImplementedError for an outlier error model."""
+    who = 'heldout_transformed'
+    freq, A = _heldout_grid(problem, freq_test, A_test_blocks, who)
+    params = np.atleast_2d(_lib.f64(params))
+    if params.ndim != 2 or params.shape[1] != problem.D:
+        raise ValueError('%s: params must be [B, %d], not %s' % (who, problem.D, params.shape))
+    B, H = params.shape[0], len(freq)
+    Zh, sg = np.empty((B, 2 * H)), np.empty((B, 2 * H))
+    _lib.check(problem._lib.bdrt_heldout_transformed(problem.handle, _lib.ptr(params), B, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(Zh),
+                                                     _lib.ptr(sg)), 'bdrt_heldout_transformed')
+    return Zh, sg
+
+
+def heldout_reduce(Zhat, sig, z, unit='frequency'):
+    """The predictive of held-out units under equal weights on the GPU (bdrt_heldout_reduce): Zhat, sig [G, S, N2] and z [G, N2]
+    (or [S, N2] and [N2]: G = 1).  Returns a dict of lpd [G, units] = logsumexp_s(ll_s) - log S and mean, sd, pit [G, N2] of the
+    mixture of the draws' normals -- `psis_loo`'s lpd and `psis_predict`'s mean_post, sd_post, pit_post to the bit, without the
+    Pareto fit.  A unit with a non-finite log-likelihood gives NaN, that unit only."""
+    pair = _pair(unit)
+    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
+    one = Zhat.ndim == 2
+    if one:
+        Zhat, sig, z = Zhat[None], sig[None], z[None]
+    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
+        raise ValueError('heldout_reduce: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+    G, S, N2 = Zhat.shape
+    if pair and N2 % 2:
+        raise ValueError("heldout_reduce: unit='frequency' needs an even number of columns, not %d" % N2)
+    if G < 1 or N2 < 1:
+        raise ValueError('heldout_reduce: empty input')
+    _heldout_draw_count(S, 'heldout_reduce')
+    lib = _lib.require_gpu()
+    lpd = np.empty((G, N2 // 2 if pair else N2))
+    outs = [np.empty((G, N2)) for _ in HELDOUT_FIELDS]
+    _lib.check(lib.bdrt_heldout_reduce(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, _lib.ptr(lpd),
+                                       *[_lib.ptr(o) for o in outs]), 'bdrt_heldout_reduce')
+    res = dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
+    return {key: v[0] for key, v in res.items()} if one else res
+
+
+def _heldout_part(unit, part, H, who):
+    """(pair, first column, columns) of the part in the 2 H held-out columns; the checks of `check_device_args`."""
+    pair, _ = check_device_args(unit, part, None, who)
+    col0, ncols = {'both': (0, 2 * H), 'real': (0, H), 'imag': (H, H)}[part]
+    return pair, col0, ncols
+
+
+def sampler_heldout(sampler, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both',
+                    chunk_bytes=None):
+    """`heldout_reduce(heldout_transformed(...))` of the draws a sampler holds in HBM (bdrt_sampler_heldout): units
+    [unit_lo, unit_hi) in groups of `chains` consecutive units that sampled one spectrum, against z_test [G, 2 H] (or [2 H] for
+    one group), the held-out data on each group's scale.  Per chunk of groups the batch evaluator gives the constrained
+    parameters of the rows, and nothing but the per-unit results comes back.  part: 'both', or 'real' / 'imag' for that half
+    of the scalars (units are points then).  Returns `heldout_reduce`'s dict, lpd [G, units], the others [G, columns of the
+    part]; every entry equals `host_heldout` on the downloaded draws bit for bit."""
+    who = 'heldout'
+    freq, A = _heldout_grid(sampler.problem, freq_test, A_test_blocks, who)
+    H = len(freq)
+    pair, col0, ncols = _heldout_part(unit, part, H, who)
+    chains, unit_lo, unit_hi = int(chains), int(unit_lo), int(unit_hi)
+    if chains < 1 or unit_lo < 0 or unit_hi > sampler.n_units or unit_hi <= unit_lo or (unit_hi - unit_lo) % chains:
+        raise ValueError('%s: units [%d, %d) do not split into groups of %d chains' % (who, unit_lo, unit_hi, chains))
+    G = (unit_hi - unit_lo) // chains
+    z = np.atleast_2d(_lib.f64(z_test))
+    if z.shape != (G, 2 * H):
+        raise ValueError('%s: z_test must be [%d, %d] (real halves, then imaginary halves), not %s' % (who, G, 2 * H, z.shape))
+    chunk = chunk_or_default(chunk_bytes)
+    if sampler.n_draws < 1:
+        raise ValueError('%s: the sampler holds no draws' % who)
+    _heldout_draw_count(chains * sampler.n_draws, who)
+    lpd = np.empty((G, ncols // 2 if pair else ncols))
+    outs = [np.empty((G, ncols)) for _ in HELDOUT_FIELDS]
+    _lib.check(sampler._lib.bdrt_sampler_heldout(sampler.handle, unit_lo, unit_hi, chains, pair, col0, ncols,
+                                                 chunk, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(z),
+                                                 _lib.ptr(lpd), *[_lib.ptr(o) for o in outs]), 'bdrt_sampler_heldout')
+    return dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
+
+
+def host_heldout(problem, draws, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both'):
+    """What `sampler_heldout` computes, on host-resident unconstrained draws [G, chains * n_draws, D] through the host-staged
+    entry points (`Problem.transformed` for the constrained parameters, `heldout_transformed`, `heldout_reduce`): the yardstick
+    of the device path."""
+    who = 'heldout'
+    freq, _ = _heldout_grid(problem, freq_test, A_test_blocks, who)
+    H = len(freq)
+    _, col0, ncols = _heldout_part(unit, part, H, who)
+    draws, z = np.asarray(draws, dtype=float), np.atleast_2d(np.asarray(z_test, dtype=float))
+    if draws.ndim != 3 or draws.shape[2] != problem.D or z.shape != (draws.shape[0], 2 * H):
+        raise ValueError('%s: draws must be [G, S, %d] and z_test [G, %d]' % (who, problem.D, 2 * H))
+    _heldout_draw_count(draws.shape[1], who)
+    cols = slice(col0, col0 + ncols)
+    tr = [heldout_transformed(problem, problem.transformed(d)[0], freq, A_test_blocks) for d in draws]
+    return heldout_reduce(np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
+                          np.ascontiguousarray(np.stack([t[1] for t in tr])[:, :, cols]), np.ascontiguousarray(z[:, cols]), unit)
+
+
 def _host_arrays(problem, draws, z, part):
     """Z_hat, sigma_tot [G, S, columns] and z [G, columns] of host-resident unconstrained draws [G, S, D]: `transformed` per
     group, as `StanFit['Z_hat']` calls it, then the columns of the part."""
@@ -488,6 +635,137 @@ def loo_predict_many(fits, zs, chains=None, unit='frequency', reff='auto', colum
             for g, i in enumerate(sel):
                 out[i] = _predict_result({k: v[g] for k, v in p.items()}, zz[g], shape[0], frequencies[i], 'fit %d: ' % i)
     return out
+
+# ---------------------------------------------------------------------------------------------------- K-fold and exact refits
+def heldout_result(p, z, frequencies, part, unit, S, z_scale):
+    """One group's row of `heldout_reduce`'s dict (lpd [units], mean, sd, pit [columns of the part]) against the scaled held-out
+    data z [columns of the part] -> LooResult in the units of the impedance as supplied: frequencies, elpd (the sum), elpd_i per
+    unit (log(z_scale) subtracted once per scalar), Z_pred (complex), sigma_pred_re/_im, pit_re/_im, resid_re/_im, n_draws.
+    part 'real' / 'imag': the other half is NaN and units are points."""
+    pair, _ = check_device_args(unit, part, None, 'heldout')
+    freq = np.array(frequencies, dtype=float).reshape(-1)
+    H, sc = len(freq), float(z_scale)
+    half = {'real': ('re',), 'imag': ('im',), 'both': ('re', 'im')}[part]
+    z, lpd = np.asarray(z, dtype=float).reshape(-1), np.asarray(p['lpd'], dtype=float).reshape(-1)
+    if len(z) != H * len(half) or len(lpd) != (H if pair else len(z)) or any(np.shape(p[k]) != z.shape for k in HELDOUT_FIELDS):
+        raise ValueError('heldout_result: the arrays do not fit %d frequencies, part %r, unit %r' % (H, part, unit))
+    nan = np.full(H, np.nan)
+
+    def parts(v):
+        v = np.asarray(v, dtype=float)
+        return {'re': v[:H] if 're' in half else nan, 'im': v[H * (len(half) - 1):] if 'im' in half else nan}
+    with np.errstate(invalid='ignore', divide='ignore'):
+        resid = (z - p['mean']) / p['sd']
+    elpd_i = lpd - (2 if pair else 1) * float(np.log(sc))
+    m, sd, pit, rs = parts(p['mean']), parts(p['sd']), parts(p['pit']), parts(resid)
+    out = LooResult(frequencies=freq, elpd=float(np.sum(elpd_i)), elpd_i=elpd_i, n_draws=int(S), unit=unit, part=part)
+    out['Z_pred'] = np.empty(H, dtype=complex)                              # (a NaN half must not spread to the other)
+    out['Z_pred'].real, out['Z_pred'].imag = m['re'] * sc, m['im'] * sc
+    for h in ('re', 'im'):
+        out['sigma_pred_' + h], out['pit_' + h], out['resid_' + h] = sd[h] * sc, pit[h], rs[h]
+    return out
+
+
+def fold_labels(frequencies, folds=10):
+    """The fold of every frequency, in the order given, without random numbers: with an integer `folds` the frequencies are
+    sorted in descending order and sorted index i goes to fold i % folds, so every fold spans the whole range; or `folds` is an
+    integer array with one label per frequency.  ValueError for fewer than two folds, for a fold that would be empty or leave no
+    training data, and for a label array of the wrong length."""
+    f = np.asarray(frequencies, dtype=float).reshape(-1)
+    n = len(f)
+    if np.ndim(folds) == 0:
+        k = int(folds)
+        if k != folds or k < 2:
+            raise ValueError('kfold: folds must be an integer of at least 2 or an array of fold labels, not %r' % (folds,))
+        if k > n:
+            raise ValueError('kfold: %d folds for %d frequencies: a fold would be empty' % (k, n))
+        labels = np.empty(n, dtype=int)
+        labels[np.argsort(-f, kind='stable')] = np.arange(n) % k
+        return labels
+    lab = np.asarray(folds)
+    if lab.ndim != 1 or len(lab) != n:
+        raise ValueError('kfold: %d fold labels for %d frequencies' % (lab.size, n))
+    if not np.issubdtype(lab.dtype, np.integer):
+        if not np.all(np.isfinite(lab.astype(float))) or np.any(lab.astype(float) != np.round(lab.astype(float))):
+            raise ValueError('kfold: fold labels must be integers')
+    lab = lab.astype(int)
+    if len(np.unique(lab)) < 2:
+        raise ValueError('kfold: at least 2 folds are needed: one fold alone leaves no training data')
+    return lab
+
+
+def kfold_result(labels, fold_results, unit='frequency', part='both'):
+    """The `heldout_result`s of the folds of ONE spectrum -> its K-fold LooResult, in the order of the supplied grid.
+    labels [n]: `fold_labels`; fold_results {label: heldout_result of the frequencies with that label, in grid order}.
+    Carries what `compare` reads -- elpd_loo (the sum of the folds' elpd_i), se, elpd_i, n_units; p_loo NaN, pareto_k all NaN,
+    n_bad_k 0 --, method='kfold', the `fold` of every unit and the predictive arrays of `heldout_result`."""
+    pair, _ = check_device_args(unit, part, None, 'kfold')
+    labels = np.asarray(labels, dtype=int)
+    n = len(labels)
+    both_points = part == 'both' and not pair
+    n_units = 2 * n if both_points else n
+    elpd_i = np.full(n_units, np.nan)
+    filled = np.zeros(n, dtype=int)
+    arrays = {k: np.full(n, np.nan, dtype=complex if k == 'Z_pred' else float)
+              for k in ('Z_pred', 'sigma_pred_re', 'sigma_pred_im', 'pit_re', 'pit_im', 'resid_re', 'resid_im')}
+    freq = np.full(n, np.nan)
+    n_draws = None
+    if set(fold_results) != set(np.unique(labels).tolist()):
+        raise ValueError('kfold_result: folds %s, labels %s' % (sorted(fold_results), np.unique(labels).tolist()))
+    for lab, r in fold_results.items():
+        idx = np.nonzero(labels == lab)[0]
+        e = np.asarray(r['elpd_i'])
+        if len(e) != (2 * len(idx) if both_points else len(idx)):
+            raise ValueError('kfold_result: fold %r has %d units for %d frequencies' % (lab, len(e), len(idx)))
+        filled[idx] += 1
+        if both_points:
+            elpd_i[idx], elpd_i[n + idx] = e[:len(idx)], e[len(idx):]
+        else:
+            elpd_i[idx] = e
+        for k in arrays:
+            arrays[k][idx] = r[k]
+        freq[idx] = r['frequencies']
+        n_draws = int(r['n_draws']) if n_draws is None else min(n_draws, int(r['n_draws']))
+    if not np.all(filled == 1):
+        raise ValueError('kfold_result: every frequency must be held out exactly once')
+    return LooResult(elpd_loo=float(np.sum(elpd_i)), se=float(np.sqrt(n_units * np.var(elpd_i))), p_loo=float('nan'),
+                     n_units=int(n_units), n_draws=n_draws, elpd_i=elpd_i, pareto_k=np.full(n_units, np.nan), n_bad_k=0,
+                     method='kfold', fold=np.concatenate([labels, labels]) if both_points else labels.copy(), frequencies=freq,
+                     unit=unit, part=part, **arrays)
+
+
+def reloo_candidates(loo_result, k_threshold=K_THRESHOLD, max_refits=8):
+    """Indices of the units of a `LooResult` whose Pareto k exceeds k_threshold: those an exact refit repairs.  ValueError when
+    there are more than max_refits (None: no cap)."""
+    with np.errstate(invalid='ignore'):
+        cand = np.nonzero(np.asarray(loo_result['pareto_k'], dtype=float) > k_threshold)[0]
+    if max_refits is not None and len(cand) > int(max_refits):
+        raise ValueError('reloo: %d observations have Pareto k > %g, more than max_refits = %d exact refits: raise max_refits '
+                         '(None lifts the cap), or use kfold, the cheaper route when so many are flagged'
+                         % (len(cand), k_threshold, int(max_refits)))
+    return cand
+
+
+def reloo_result(loo_result, exact):
+    """`LooResult` of `loo` with elpd_i replaced by exact values at refit units: exact {unit index: elpd_i of a fit without that
+    unit}.  elpd_loo, se, p_loo (the sum of lpd_i - elpd_i) and n_bad_k (units still above 0.7 and not refit) are recomputed;
+    lpd_i, pareto_k, the WAIC entries and every other elpd_i keep their bits.  Adds the boolean `refit` [n_units] and
+    method='psis+refit'."""
+    res = LooResult(loo_result)
+    elpd_i = np.array(loo_result['elpd_i'], dtype=float)
+    n = len(elpd_i)
+    refit = np.zeros(n, dtype=bool)
+    for i, v in exact.items():
+        if not 0 <= int(i) < n:
+            raise ValueError('reloo_result: unit %r of %d' % (i, n))
+        elpd_i[int(i)] = float(v)
+        refit[int(i)] = True
+    with np.errstate(invalid='ignore'):
+        bad = (np.asarray(loo_result['pareto_k'], dtype=float) > K_THRESHOLD) & ~refit
+    res.update(elpd_i=elpd_i, elpd_loo=float(np.sum(elpd_i)), se=float(np.sqrt(n * np.var(elpd_i))),
+               p_loo=float(np.sum(np.asarray(loo_result['lpd_i'], dtype=float) - elpd_i)), n_bad_k=int(np.sum(bad)), refit=refit,
+               method='psis+refit')
+    return res
 
 
 def compare(results):

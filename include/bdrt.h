@@ -404,6 +404,31 @@ int bdrt_sampler_loo_predict(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
                              double *mean_post, double *sd_post, double *pit_post, double *pareto_k, int *n_tail, double *reff_out);
 /* device bytes one group adds to a chunk of the two entry points above (predict != 0: of bdrt_sampler_loo_predict); 0: bad arguments */
 size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict);
+/* ---- (4b) held-out frequencies: exact leave-out refits and K-fold cross-validation -----
+ * Definitions: tests/heldout_numpy.py.  A fold is a sampling fit on a training grid; these entries say what its draws predict
+ * at H frequencies that are not on it.  Outlier error models are refused (-2): a held-out point has no sigma_out of its own.
+ *
+ * Z_hat and sigma_tot [B][2H] (real halves, then imaginary halves) of B rows of constrained parameters, params [B][D] in the
+ * layout bdrt_transformed writes, at freq_test [H] (Hz, positive).  A_test: the prediction rows, per block [2H][K_b] row-major
+ * (real rows, then imaginary rows), block after block.  Block flags, x_scale, induc_scale and sigma_min are the problem's.
+ * A row's result does not depend on its place in the launch. */
+int bdrt_heldout_transformed(bdrt_problem *p, const double *params, int B, const double *freq_test, int H, const double *A_test,
+                             double *Z_hat, double *sigma_tot);
+/* The predictive of held-out units under equal weights: Zhat, sig [G][S][N2] and z [G][N2] on the host, units as in
+ * bdrt_psis_predict (pair).  lpd [G][U] = logsumexp_s(ll_s) - log S, equal to bdrt_psis_loo's lpd on bdrt_pointwise_loglik's
+ * output to the bit; mean, sd, pit [G][N2] equal bdrt_psis_predict's mean_post, sd_post, pit_post to the bit.  No Pareto fit is
+ * run.  A unit with a non-finite log-likelihood gives NaN in its outputs, that unit only.  2 <= S <= bdrt_psis_loo_max_draws()
+ * (-2 above). */
+int bdrt_heldout_reduce(const double *Zhat, const double *sig, const double *z, int G, int S, int N2, int pair, double *lpd,
+                        double *mean, double *sd, double *pit);
+/* Both on the draws a sampler holds, in chunks of groups as bdrt_sampler_loo: per chunk the batch evaluator gives the
+ * constrained parameters of the rows, bdrt_heldout_transformed's kernel their Z_hat and sigma_tot at freq_test, and
+ * bdrt_heldout_reduce's kernel the results against z_test [G][2H] (host), scalar columns [col0, col0 + ncols) of the 2H (the
+ * real half, the imaginary half or all; pair = 1 needs all).  Outputs on the host: lpd [G][U], mean, sd, pit [G][ncols]; each
+ * equals the two host-staged entries on the downloaded draws bit for bit.  chunk_bytes: 0: 1 GiB. */
+int bdrt_sampler_heldout(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                         size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, double *lpd,
+                         double *mean, double *sd, double *pit);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
