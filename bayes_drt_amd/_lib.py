@@ -101,6 +101,7 @@ SYMBOLS = [
     'bdrt_debug_hessian', 'bdrt_debug_hessian_lin', 'bdrt_debug_rank_z',
     'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept', 'bdrt_debug_qp_factor_solve',
     'bdrt_heldout_transformed', 'bdrt_heldout_reduce', 'bdrt_sampler_heldout',
+    'bdrt_heldout_mix_max_nodes', 'bdrt_heldout_mix_transformed', 'bdrt_heldout_mix_reduce', 'bdrt_sampler_heldout_mix',
 ]
 
 
@@ -233,6 +234,14 @@ def load_library():
     lib.bdrt_heldout_reduce.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     # (sampler, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, chunk_bytes, freq_test, H, A_test, z_test), then the outputs
     lib.bdrt_sampler_heldout.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp] + [vp] * 4
+    # the same under an outlier error model: ..., shared, y, w, Q, ey2 in front of the outputs
+    lib.bdrt_heldout_mix_max_nodes.argtypes = []
+    lib.bdrt_heldout_mix_max_nodes.restype = C.c_int
+    lib.bdrt_heldout_mix_transformed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    mix_table = [C.c_int, vp, vp, C.c_int, C.c_double]
+    lib.bdrt_heldout_mix_reduce.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + mix_table + [vp] * 4
+    lib.bdrt_sampler_heldout_mix.argtypes = ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp]
+                                             + mix_table + [vp] * 4)
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

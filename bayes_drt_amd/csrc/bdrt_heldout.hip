@@ -17,7 +17,8 @@
 //                          log-likelihoods as predict_kernel forms them, lpd as psis_kernel sums it, mean, sd and pit as
 //                          predict_kernel's equal-weight sums -- the same statements in the same order (bdrt_psis.h,
 //                          bdrt_stats.h), hence the same bits; no select, no sort, no Pareto fit.
-// bdrt_sampler_heldout runs both on a sampler's draws in chunks of groups (heldout_of_draws), as loo_of_draws does.
+// bdrt_sampler_heldout runs both on a sampler's draws in chunks of groups (heldout_of_draws), as loo_of_draws does; the loop
+// itself (heldout_of_draws_with) takes the reduction from its caller, so that bdrt_heldout_mix.hip runs its own through it.
 #include <cfloat>
 #include <cmath>
 
@@ -188,9 +189,9 @@ __global__ __launch_bounds__(LO_NT) void heldout_reduce_kernel(HeldoutReduceArgs
 // ---- device-pointer cores: each enqueues on `stream` and returns; the caller synchronises
 // dPar [B][D], dW [H] (2 pi f), dA (packed as HeldoutArgs::A) -> dZh, dSg [B][2H]
 int heldout_transformed_device(const char *who, Problem &P, const double *dPar, size_t B, const double *dW, const double *dA, int H,
-                               double *dZh, double *dSg, hipStream_t stream)
+                               double *dZh, double *dSg, hipStream_t stream, bool allow_outliers)
 {
-    if (P.dev.outlier_mode) {
+    if (P.dev.outlier_mode && !allow_outliers) {
         set_error("%s: outlier error models are refused: a held-out point has no sigma_out of its own", who);
         return -2;
     }
@@ -239,7 +240,7 @@ int heldout_reduce_device(const double *dTm, const double *dTs, const double *dz
 }
 
 // host copies of the held-out grid -> device: w = 2 pi f [H] and the packed prediction rows
-static int heldout_upload_grid(const Problem &P, const double *freq, int H, const double *A, DevBuf<double> &dW, DevBuf<double> &dA)
+int heldout_upload_grid(const Problem &P, const double *freq, int H, const double *A, DevBuf<double> &dW, DevBuf<double> &dA)
 {
     std::vector<double> w((size_t)H);
     for (int h = 0; h < H; ++h) w[h] = 2.0 * M_PI * freq[h];
@@ -269,7 +270,17 @@ static size_t heldout_group_bytes(const LooDraws &j, int H)
 int heldout_of_draws(const LooDraws &j, const double *freq, int H, const double *A, const double *z_test, double *lpd, double *mean,
                      double *sd, double *pit)
 {
-    const char *who = "bdrt_sampler_heldout";
+    return heldout_of_draws_with("bdrt_sampler_heldout", j, freq, H, A, z_test, false,
+                                 [&](const double *dTm, const double *dTs, const double *dz, int gn, int S, double *dOut) {
+                                     return heldout_reduce_device(dTm, dTs, dz, gn, S, j.ncols, j.pair, dOut, j.stream);
+                                 }, lpd, mean, sd, pit);
+}
+
+// the same with the reduction of a chunk's groups left to the caller (bdrt_heldout_mix.hip has another); allow_outliers: sg is then
+// the base scale
+int heldout_of_draws_with(const char *who, const LooDraws &j, const double *freq, int H, const double *A, const double *z_test,
+                          bool allow_outliers, const HeldoutReduceFn &reduce, double *lpd, double *mean, double *sd, double *pit)
+{
     Problem &P = *j.prob;
     BDRT_HIP(hipSetDevice(P.device));
     const int S = j.chains * j.n_draws, U = j.pair ? j.ncols / 2 : j.ncols;
@@ -296,10 +307,10 @@ int heldout_of_draws(const LooDraws &j, const double *freq, int H, const double 
         int rc;
         if ((rc = launch_logp_grad(&P, j.draws + (size_t)g0 * S * P.dev.D, nullptr, (int)((size_t)gn * S), 0, lp, nullptr, par, nullptr, nullptr,
                                    j.stream)) ||
-            (rc = heldout_transformed_device(who, P, par, (size_t)gn * S, dW, dA, H, zh, sg, j.stream)) ||
+            (rc = heldout_transformed_device(who, P, par, (size_t)gn * S, dW, dA, H, zh, sg, j.stream, allow_outliers)) ||
             (rc = loo_transpose_device(who, zh.p + j.col0, Tm, gn, S, j.ncols, N2, j.stream)) ||
             (rc = loo_transpose_device(who, sg.p + j.col0, Ts, gn, S, j.ncols, N2, j.stream)) ||
-            (rc = heldout_reduce_device(Tm, Ts, dz.p + osc, gn, S, j.ncols, j.pair, out, j.stream)))
+            (rc = reduce(Tm, Ts, dz.p + osc, gn, S, out)))
             return rc;
         BDRT_HIP(hipStreamSynchronize(j.stream));
         double *const outs[3] = {mean + osc, sd + osc, pit + osc};
@@ -335,7 +346,7 @@ int bdrt_heldout_transformed(bdrt_problem *p, const double *params, int B, const
     if (heldout_upload_grid(P, freq_test, H, A_test, dW, dA) || upload(dPar, params, (size_t)B * P.dev.D)) return -10;
     BDRT_HIP(dZh.alloc(nz));
     BDRT_HIP(dSg.alloc(nz));
-    if (const int rc = heldout_transformed_device("bdrt_heldout_transformed", P, dPar, (size_t)B, dW, dA, H, dZh, dSg, P.stream)) return rc;
+    if (const int rc = heldout_transformed_device("bdrt_heldout_transformed", P, dPar, (size_t)B, dW, dA, H, dZh, dSg, P.stream, false)) return rc;
     if (download(Z_hat, dZh.p, nz, P.stream) || download(sigma_tot, dSg.p, nz, P.stream)) return -10;
     BDRT_HIP(hipStreamSynchronize(P.stream));
     return 0;

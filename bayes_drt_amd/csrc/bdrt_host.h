@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -241,9 +242,10 @@ int loo_predict_of_draws(const LooDraws &j, double *mean, double *sd, double *pi
 
 // Prediction at held-out frequencies and its equal-weight reduction (bdrt_heldout.hip).  The device-pointer cores enqueue on
 // `stream` and return.  dPar [B][D] constrained parameters, dW [H] = 2 pi f, dA per block [2H][K_b] (real rows, then imaginary
-// rows), block after block -> dZh, dSg [B][2H]; -2 for an outlier error model or a grid beyond the LDS of a CU
+// rows), block after block -> dZh, dSg [B][2H]; -2 for an outlier error model (unless allow_outliers: dSg is then the base scale,
+// sigma_tot without sigma_out, which bdrt_heldout_mix.hip integrates over its prior) or a grid beyond the LDS of a CU
 int heldout_transformed_device(const char *who, Problem &P, const double *dPar, size_t B, const double *dW, const double *dA, int H,
-                               double *dZh, double *dSg, hipStream_t stream);
+                               double *dZh, double *dSg, hipStream_t stream, bool allow_outliers);
 // dTm, dTs [G][N2][S] (transposed Z_hat, sigma_tot), dz [G][N2] -> dOut: 3 planes of G N2 (mean, sd, pit), then lpd [G U]
 int heldout_reduce_device(const double *dTm, const double *dTs, const double *dz, int G, int S, int N2, int pair, double *dOut,
                           hipStream_t stream);
@@ -253,6 +255,17 @@ int heldout_check_grid(const char *who, const double *freq, int H);
 // (reff_* unused); freq [H], A (as dA) and z_test [G][2H] on the host; outputs on the host, lpd [G][U], the others [G][ncols]
 int heldout_of_draws(const LooDraws &j, const double *freq, int H, const double *A, const double *z_test, double *lpd, double *mean,
                      double *sd, double *pit);
+// host copies of the held-out grid -> device: w = 2 pi f [H] and the packed prediction rows
+int heldout_upload_grid(const Problem &P, const double *freq, int H, const double *A, DevBuf<double> &dW, DevBuf<double> &dA);
+// heldout_of_draws with the reduction of a chunk left to the caller: reduce(dTm, dTs [gn][ncols][S], dz [gn][ncols], gn, S, dOut)
+// enqueues on j.stream what fills dOut with 3 planes of gn ncols (mean, sd, pit), then lpd [gn U]; who: the name in error texts
+using HeldoutReduceFn = std::function<int(const double *, const double *, const double *, int, int, double *)>;
+int heldout_of_draws_with(const char *who, const LooDraws &j, const double *freq, int H, const double *A, const double *z_test,
+                          bool allow_outliers, const HeldoutReduceFn &reduce, double *lpd, double *mean, double *sd, double *pit);
+// the same under an outlier error model (bdrt_heldout_mix.hip): sigma_out integrated over its prior, the table y, w [Q] with
+// second moment ey2 on the host; shared: the two scalars of a frequency have one sigma_out
+int heldout_mix_of_draws(const LooDraws &j, const double *freq, int H, const double *A, const double *z_test, int shared,
+                         const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit);
 
 // rank-normalised diagnostics (bdrt_rank.hip) of the same layout of DEVICE draws, on the split chains; outputs [G x C] on the host
 int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M,

@@ -840,6 +840,27 @@ int bdrt_sampler_heldout(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_p
     return heldout_of_draws(j, freq_test, H, A_test, z_test, lpd, mean, sd, pit);
 }
 
+int bdrt_sampler_heldout_mix(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                             size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, int shared,
+                             const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit)
+{
+    if (!freq_test || !A_test || !z_test || !y || !w || !lpd || !mean || !sd || !pit || H < 1) {
+        set_error("bdrt_sampler_heldout_mix: bad arguments");
+        return -1;
+    }
+    if (s && !s->impl.prob->dev.outlier_mode) {
+        set_error("bdrt_sampler_heldout_mix: the problem has no outlier error model: bdrt_sampler_heldout is the entry for it");
+        return -2;
+    }
+    if (heldout_check_grid("bdrt_sampler_heldout_mix", freq_test, H)) return -1;
+    std::vector<int> spec;
+    LooDraws j;
+    if (int rc = sampler_loo_job("bdrt_sampler_heldout_mix", s, unit_lo, unit_hi, chains_per_group, pair, col0, ncols, 0, nullptr,
+                                 chunk_bytes, spec, j, 2 * H))
+        return rc;
+    return heldout_mix_of_draws(j, freq_test, H, A_test, z_test, shared, y, w, Q, ey2, lpd, mean, sd, pit);
+}
+
 size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict)
 {
     if (!s || chains_per_group < 1 || ncols < 1) return 0;

@@ -562,12 +562,13 @@ class Sampler:
         from .loo import sampler_psis_predict
         return sampler_psis_predict(self, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes)
 
-    def heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both', chunk_bytes=None):
+    def heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both', chunk_bytes=None,
+                sigma_out=None):
         """What the draws of the same groups predict at frequencies that are not on the problem's grid, against the held-out
         data z_test [groups, 2 H], reduced where the draws are (bdrt_sampler_heldout): `loo.heldout_reduce`'s dict.
-        Arguments: `loo.sampler_heldout`."""
+        Arguments: `loo.sampler_heldout`; sigma_out='prior' admits an outlier error model (bdrt_sampler_heldout_mix)."""
         from .loo import sampler_heldout
-        return sampler_heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit, part, chunk_bytes)
+        return sampler_heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit, part, chunk_bytes, sigma_out)
 
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""
@@ -595,18 +596,18 @@ def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, 
     loo=dict(chains=M, loo=True, predict=False, unit=, part=, reff=, chunk_bytes=): also reduce PSIS-LOO (`Sampler.loo`) and / or
     the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; one more item, a dict
     with the entries 'loo' and / or 'predict'.
-    heldout=dict(chains=M, freq_test=, A_test_blocks=, z_test=, unit=, part=, chunk_bytes=): also reduce the predictive of held-out
-    frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; one more item (the last), its dict."""
+    heldout=dict(chains=M, freq_test=, A_test_blocks=, z_test=, unit=, part=, chunk_bytes=, sigma_out=): also reduce the predictive of
+    held-out frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; one more item (the last), its dict."""
     hkw = None
     if heldout is not None:
         hkw = dict(heldout)
         need = {'chains', 'freq_test', 'A_test_blocks', 'z_test'}
-        unknown = sorted(set(hkw) - need - {'unit', 'part', 'chunk_bytes'})
+        unknown = sorted(set(hkw) - need - {'unit', 'part', 'chunk_bytes', 'sigma_out'})
         if unknown or not need <= set(hkw):
-            raise ValueError('sample_units: heldout needs chains, freq_test, A_test_blocks, z_test and takes unit, part, chunk_bytes '
-                             '(got %s)' % sorted(hkw))
+            raise ValueError('sample_units: heldout needs chains, freq_test, A_test_blocks, z_test and takes unit, part, chunk_bytes, '
+                             'sigma_out (got %s)' % sorted(hkw))
         from .loo import _heldout_grid, _heldout_part
-        f_, _ = _heldout_grid(problem, hkw['freq_test'], hkw['A_test_blocks'], 'heldout')
+        f_, _ = _heldout_grid(problem, hkw['freq_test'], hkw['A_test_blocks'], 'heldout', hkw.get('sigma_out'))
         _heldout_part(hkw.get('unit', 'frequency'), hkw.get('part', 'both'), len(f_), 'heldout')
     kw = None
     if loo is not None:
@@ -632,7 +633,8 @@ def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, 
             res = res + (out,)
         if hkw is not None:
             res = res + (smp.heldout(0, n_units, hkw['chains'], hkw['freq_test'], hkw['A_test_blocks'], hkw['z_test'],
-                                     hkw.get('unit', 'frequency'), hkw.get('part', 'both'), hkw.get('chunk_bytes')),)
+                                     hkw.get('unit', 'frequency'), hkw.get('part', 'both'), hkw.get('chunk_bytes'),
+                                     hkw.get('sigma_out')),)
         return res
 
 

@@ -975,7 +975,7 @@ class Inverter:
             init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
             mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
             model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True,
-            loo=False, loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency'):
+            loo=False, loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None):
         """Fit the distribution(s) with the calibrated hierarchical Bayesian model: mode='optimize' (MAP) or
         'sample' (NUTS).  Arguments as in the reference (:1072-1152), plus two that only concern mode='optimize':
 
@@ -994,11 +994,11 @@ class Inverter:
             logging.getLogger('bayes_drt_amd') (bayes_drt_amd.diagnostics); False: no check.
         loo, loo_predict, loo_kw : mode='sample' only -- as in `fit_many`: `loo_result` / `loo_predict_result` reduced while
             the sampler still holds the draws.
-        heldout, heldout_unit : mode='sample' only -- as in `fit_many`: (f_test, Z_test), frequencies this fit does not see;
-            `heldout_result` is what its draws predict there."""
+        heldout, heldout_unit, heldout_sigma_out : mode='sample' only -- as in `fit_many`: (f_test, Z_test), frequencies this fit
+            does not see; `heldout_result` is what its draws predict there."""
         self._fit_argument_checks(part, mode, fitY, SA, SASY, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
-        hkw = self._heldout_arguments(heldout, heldout_unit, 1, mode, part, [outliers], None)
+        hkw = self._heldout_arguments(heldout, heldout_unit, 1, mode, part, [outliers], None, heldout_sigma_out)
         job = self._fit_prepare(frequencies, Z, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                 inductance_scale, outlier_lambda, mode, add_stan_data, model_str, fitY, SA, SASY, n_starts)
         model, dat = job['model'], job['dat']
@@ -1078,7 +1078,7 @@ class Inverter:
                  init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
                  mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
                  model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True, loo=False,
-                 loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency'):
+                 loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None):
         """The fits `[copy(self).fit(frequencies, Z, ...) for Z in Z_list]` -- the reference's own workload is such a loop
         over spectra measured on one frequency grid (code_EchemActa/Run fits.ipynb cells 4-5, inversion.py:1072-1081,
         :1218-1221) -- as ONE batch: one shared problem in HBM (the matrices are those of the common grid), every
@@ -1111,11 +1111,15 @@ class Inverter:
         (the sum) and elpd_i per unit, Z_pred (complex), sigma_pred_re/_im, pit_re/_im, resid_re/_im, n_draws, in the units of the
         impedance as supplied and in the order of f_test.  heldout_unit: 'frequency' or 'point'; with part 'real' / 'imag' the
         other half is NaN and units are points, as in `loo_predict`.  NotImplementedError for the outlier error models (a held-out
-        point has no sigma_out) and inside a process group with more than one rank."""
+        point has no sigma_out) unless heldout_sigma_out='prior', and inside a process group with more than one rank.
+        heldout_sigma_out: None, or 'prior': under an outlier error model the held-out point's sigma_out is integrated over its
+        prior, which data alone fix (`loo.sigma_out_prior_table`, `loo.heldout_mix_reduce`), and `heldout_result` carries
+        sigma_out='prior'; ValueError with outliers=False; with outliers='auto' a spectrum that ends without the outlier model
+        is reduced as without the keyword."""
         self._fit_argument_checks(part, mode, False, False, False, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
         hkw = self._heldout_arguments(heldout, heldout_unit, len(Z_list), mode, part,
-                                      self._per_spectrum(outliers, len(Z_list), 'outliers'), group)
+                                      self._per_spectrum(outliers, len(Z_list), 'outliers'), group, heldout_sigma_out)
         if hkw is not None:
             self._heldout_shared_grids(hkw, frequencies, len(Z_list), (nonneg, outliers, sigma_min, inductance_scale, outlier_lambda))
         views, jobs = self._batch_jobs(frequencies, Z_list, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
@@ -1133,7 +1137,7 @@ class Inverter:
                 f0 = hkw['pairs'][idx[0]][0]
                 if any(not np.array_equal(hkw['pairs'][i][0], f0) for i in idx[1:]):
                     raise ValueError('heldout: the spectra of one batch must share f_test (spectra %s)' % idx)
-                if any(jobs[i]['outliers'] for i in idx):
+                if hkw['sigma_out'] is None and any(jobs[i]['outliers'] for i in idx):
                     from . import loo as _loo
                     raise NotImplementedError('fit_many(heldout=...): ' + _loo.OUTLIER_REFUSAL)
         for idx in order.values():
@@ -1182,16 +1186,29 @@ class Inverter:
             _loo.logger.disabled = was
 
     @staticmethod
-    def _heldout_arguments(heldout, unit, n, mode, part, outliers, group):
-        """`heldout=` of `fit` / `fit_many` -> dict(pairs=[(f_test, Z_test) per spectrum], unit=) (None: not asked for), checked
-        before any GPU work."""
-        if heldout is None:
-            return None
+    def _heldout_outliers(outliers, sigma_out, who):
+        """The outlier options of the spectra against `sigma_out=`: None refuses outliers=True, 'prior' outliers=False; 'auto' is
+        looked at once it has decided."""
         from . import loo as _loo
+        _loo.check_sigma_out(sigma_out, who)
+        fixed = [bool(o) for o in outliers if not isinstance(o, str)]
+        if sigma_out is None and any(fixed):
+            raise NotImplementedError('%s: %s' % (who, _loo.OUTLIER_REFUSAL))
+        if sigma_out is not None and not all(fixed):
+            raise ValueError("%s: sigma_out='prior' needs an outlier error model (outliers=True or 'auto'), not outliers=False" % who)
+
+    @staticmethod
+    def _heldout_arguments(heldout, unit, n, mode, part, outliers, group, sigma_out=None):
+        """`heldout=` of `fit` / `fit_many` -> dict(pairs=[(f_test, Z_test) per spectrum], unit=, sigma_out=) (None: not asked
+        for), checked before any GPU work."""
+        from . import loo as _loo
+        if heldout is None:
+            if sigma_out is not None:
+                raise ValueError('heldout_sigma_out is given, but heldout is not set')
+            return None
         if mode != 'sample':
             raise ValueError("heldout needs the draws of mode='sample'; the predictive of a MAP fit is not defined here")
-        if any(not isinstance(o, str) and bool(o) for o in outliers):            # ('auto' is looked at once it has decided)
-            raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
+        Inverter._heldout_outliers(outliers, sigma_out, 'fit(heldout=...)')
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -1223,7 +1240,7 @@ class Inverter:
                 raise ValueError('heldout: f_test and Z_test must have the same length, at least 1')
             _validate_spectrum(f, Z)
             out.append((f, Z))
-        return dict(pairs=out, unit='point' if part != 'both' else unit)
+        return dict(pairs=out, unit='point' if part != 'both' else unit, sigma_out=sigma_out)
 
     @classmethod
     def _heldout_shared_grids(cls, hkw, frequencies, n, options):
@@ -1256,8 +1273,11 @@ class Inverter:
         `_get_prediction_matrices`, and the held-out data of every spectrum on that spectrum's own scale (`scale_Z` has seen the
         training rows only)."""
         from . import loo as _loo
-        if any(job['outliers'] for job in jobs):
+        with_outliers = [bool(job['outliers']) for job in jobs]
+        if hkw.get('sigma_out') is None and any(with_outliers):
             raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
+        if any(with_outliers) != all(with_outliers):
+            raise ValueError('heldout: the spectra of one batch must share the error model')
         f0 = hkw['pairs'][0][0]
         if any(len(f) != len(f0) or not np.array_equal(f, f0) for f, _ in hkw['pairs'][1:]):
             raise ValueError('heldout: the spectra of one batch must share f_test')
@@ -1266,7 +1286,10 @@ class Inverter:
         pm = views[0]._get_prediction_matrices(f0, names)
         A = [np.concatenate((keep_re * pm[n]['A_re'], keep_im * pm[n]['A_im'])) for n in names]
         z = np.vstack([np.concatenate((keep_re * Z.real, keep_im * Z.imag)) / inv._Z_scale for inv, (_, Z) in zip(views, hkw['pairs'])])
-        return dict(chains=chains, freq_test=f0, A_test_blocks=A, z_test=z, unit=hkw['unit'], part=part)
+        held = dict(chains=chains, freq_test=f0, A_test_blocks=A, z_test=z, unit=hkw['unit'], part=part)
+        if hkw.get('sigma_out') is not None and all(with_outliers):          # (outliers='auto' that chose the plain model: as without)
+            held['sigma_out'] = hkw['sigma_out']
+        return held
 
     def _store_heldout(self, res, g, held, S):
         """Row g of `Sampler.heldout`'s dict -> `heldout_result`."""
@@ -1274,7 +1297,7 @@ class Inverter:
         H, part = len(held['freq_test']), held['part']
         cols = {'both': slice(0, 2 * H), 'real': slice(0, H), 'imag': slice(H, 2 * H)}[part]
         self.heldout_result = _loo.heldout_result({k: v[g] for k, v in res.items()}, held['z_test'][g][cols], held['freq_test'], part,
-                                                  held['unit'], S, self._Z_scale)
+                                                  held['unit'], S, self._Z_scale, held.get('sigma_out'))
 
     @staticmethod
     def _batch_key(job):
@@ -2092,27 +2115,29 @@ class Inverter:
         return inv
 
     @staticmethod
-    def _refit_kw(fit_kw, who):
+    def _refit_kw(fit_kw, who, sigma_out=None):
         kw = dict(fit_kw)
         if kw.setdefault('mode', 'sample') != 'sample':
             raise ValueError("%s needs mode='sample': the folds are sampling fits" % who)
-        for k in ('heldout', 'heldout_unit', 'group'):
+        for k in ('heldout', 'heldout_unit', 'heldout_sigma_out', 'group'):
             if k in kw:
                 raise ValueError('%s: %s is set by %s itself' % (who, k, who))
-        if any(not isinstance(o, str) and bool(o) for o in np.atleast_1d(np.asarray(kw.get('outliers', False), dtype=object))):
-            from . import loo as _loo
-            raise NotImplementedError('%s: %s' % (who, _loo.OUTLIER_REFUSAL))
+        Inverter._heldout_outliers(np.atleast_1d(np.asarray(kw.get('outliers', False), dtype=object)).tolist(), sigma_out, who)
+        if sigma_out is not None:
+            kw['heldout_sigma_out'] = sigma_out
         kw.setdefault('check_outliers', False)
         return kw
 
-    def kfold_many(self, frequencies, Z_list, folds=10, unit='frequency', **fit_kw):
+    def kfold_many(self, frequencies, Z_list, folds=10, unit='frequency', sigma_out=None, **fit_kw):
         """K-fold cross-validation of many spectra on ONE grid: for each fold one `fit_many` batch of all spectra on the
         training rows with `heldout=` the fold's rows -- `folds` engine calls, not folds x spectra --, reduced on the GPU while
         the sampler holds the draws.  Fold assignment has no random numbers (`loo.fold_labels`): the frequencies sorted in
         descending order, sorted index i in fold i % folds, so every fold spans the whole range; or `folds` is an integer array,
         one fold label per frequency in the order given.  Every fold fits the same model: the basis is pinned to that of the full
         grid and only the data rows shrink; every fold has its own Z scale, as `scale_Z` looks at the training rows only.
-        fit_kw: arguments of `fit_many` (mode='sample' is implied; outlier error models raise NotImplementedError).
+        fit_kw: arguments of `fit_many` (mode='sample' is implied; outlier error models raise NotImplementedError unless
+        sigma_out='prior', `fit_many`'s heldout_sigma_out: the held-out point's sigma_out is integrated over its prior and the
+        result carries sigma_out='prior', so that `loo.compare` can rank outliers=True against outliers=False).
         Returns a list of Inverter objects (shallow copies of this one, without fit attributes of their own), one per spectrum,
         each with `kfold_result`: a `LooResult` that `loo.compare` ranks -- elpd_loo (the sum of the folds' elpd_i), se, elpd_i
         in the order of the supplied grid, n_units; p_loo NaN, pareto_k all NaN, n_bad_k 0 -- with method='kfold', the `fold` of
@@ -2126,7 +2151,7 @@ class Inverter:
         for Z in Z_list:
             _validate_spectrum(f, Z)
         labels = _loo.fold_labels(f, folds)
-        kw = self._refit_kw(fit_kw, 'kfold')
+        kw = self._refit_kw(fit_kw, 'kfold', sigma_out)
         part = kw.get('part', 'both')
         hunit = 'point' if part != 'both' else unit
         _loo.check_device_args(hunit, part, None, 'kfold')
@@ -2150,12 +2175,12 @@ class Inverter:
             out.append(inv)
         return out
 
-    def kfold(self, frequencies, Z, folds=10, unit='frequency', **fit_kw):
+    def kfold(self, frequencies, Z, folds=10, unit='frequency', sigma_out=None, **fit_kw):
         """`kfold_many` of one spectrum: stores the result as `kfold_result` of THIS instance and returns it."""
-        self.kfold_result = self.kfold_many(frequencies, [Z], folds=folds, unit=unit, **fit_kw)[0].kfold_result
+        self.kfold_result = self.kfold_many(frequencies, [Z], folds=folds, unit=unit, sigma_out=sigma_out, **fit_kw)[0].kfold_result
         return self.kfold_result
 
-    def reloo(self, frequencies, Z, k_threshold=0.7, max_refits=8, **fit_kw):
+    def reloo(self, frequencies, Z, k_threshold=0.7, max_refits=8, sigma_out=None, **fit_kw):
         """Exact leave-one-out for the frequencies PSIS flags: for every unit of this instance's `loo_result` with
         pareto_k > k_threshold one refit without that frequency (`fit(..., heldout=...)` on a copy whose basis is pinned to the
         full grid), whose `heldout_result` replaces the unit's elpd_i.  Every refit has its own grid, so they run one after the
@@ -2164,7 +2189,9 @@ class Inverter:
         `fit(..., loo=True)`) of a fit of (frequencies, Z); fit_kw: the arguments that fit was run with (mode='sample' is implied).
         elpd_loo, se, p_loo (the sum of lpd_i - elpd_i) and n_bad_k (units still above 0.7 and not refit) are recomputed; lpd_i,
         pareto_k, the WAIC entries and every untouched elpd_i keep their bits; `refit` [n_units] marks the replaced units and
-        method is 'psis+refit'.  Stores and returns the new `loo_result`."""
+        method is 'psis+refit'.  sigma_out='prior': the refits of an outlier error model predict with sigma_out integrated over its
+        prior (`fit_many`'s heldout_sigma_out); without it these models raise NotImplementedError.  Stores and returns the new
+        `loo_result`."""
         from . import loo as _loo
         r = getattr(self, 'loo_result', None)
         f, Z = np.asarray(frequencies, dtype=float), np.asarray(Z)
@@ -2173,7 +2200,7 @@ class Inverter:
                 getattr(self, '_loo_unit_part', None) != ('frequency', 'both'):
             raise ValueError("reloo needs this instance's loo_result per frequency of the supplied grid: call "
                              "loo(unit='frequency', part='both') (or fit(..., loo=True)) first")
-        kw = self._refit_kw(fit_kw, 'reloo')
+        kw = self._refit_kw(fit_kw, 'reloo', sigma_out)
         if kw.get('part', 'both') != 'both':
             raise ValueError("reloo needs unit='frequency', part='both': call loo(unit='frequency', part='both') first")
         cand = _loo.reloo_candidates(r, k_threshold, max_refits)

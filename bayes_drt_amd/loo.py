@@ -33,9 +33,12 @@ draws of a fit on a training grid predict at frequencies that are not on it -- Z
 (bdrt_heldout.hip), then the equal-weight mixture of the draws' normals: lpd, mean, sd and PIT per held-out unit.  This is the
 exact remedy for observations PSIS flags: `Inverter.reloo` refits without each of them, `Inverter.kfold_many` runs K folds of
 many spectra as K batches; both give `LooResult`s that `compare` ranks.  Definitions: tests/heldout_numpy.py.  Outlier error
-models are refused: every training point has its own sigma_out and a held-out point has none.
+models are refused by default: every training point has its own sigma_out and a held-out point has none.  With the keyword
+sigma_out='prior' a held-out point's sigma_out is integrated over its prior, which data alone fix (`sigma_out_prior_table`,
+`heldout_mix_reduce`, bdrt_heldout_mix.hip; tests/heldout_mix_numpy.py).
 
-Out of scope: moment matching for high-k observations; held-out prediction for outlier error models; stacking weights; LOO of
+Out of scope: moment matching for high-k observations; a marginal PSIS-LOO for the outlier error models (the point's own
+sigma_out integrated out of the importance ratios); stacking weights; LOO of
 MAP or ridge fits; predictive checks with replicated data, plots, and a `fit_many` that keeps no draws at all.
 """
 import logging
@@ -273,11 +276,87 @@ OUTLIER_REFUSAL = ('held-out prediction is not defined for the outlier error mod
                    'own sigma_out and a held-out point has none')
 
 
-def _heldout_grid(problem, freq_test, A_test_blocks, who):
+def _outlier_mode(problem):
+    return int(getattr(getattr(problem, 'dat', None), 'outlier_mode', 0))
+
+
+def check_sigma_out(sigma_out, who):
+    """The `sigma_out=` keyword of the held-out entries: None (the outlier error models are refused) or 'prior' (their
+    sigma_out is integrated over its prior, `sigma_out_prior_table`).  ValueError for anything else."""
+    if sigma_out is not None and not (isinstance(sigma_out, str) and sigma_out == 'prior'):
+        raise ValueError("%s: sigma_out must be None or 'prior', not %r" % (who, sigma_out))
+    return sigma_out
+
+
+def sigma_out_table(mode, so_lambda, so_alpha=5.0, so_beta=1.0, step=0.125):
+    """The prior of sigma_out as an integration rule -> (y [Q], w [Q], E[y^2], shared): sum_j w_j f(y_j) ~ E f(sigma_out).
+
+    mode 1 (`Series*_outliers`): sigma_out = 0.05 raw scale, raw ~ exponential(so_lambda), scale ~ inv_gamma(so_alpha, so_beta).
+    raw / (1 / scale) with 1 / scale ~ gamma(so_alpha, rate so_beta): P(y > t) = (1 + t / s)^-so_alpha, s = 0.05 so_beta /
+    so_lambda -- a Lomax distribution; E[y^2] = 2 s^2 / ((so_alpha - 1) (so_alpha - 2)), +inf for so_alpha <= 2.  One y is shared by the
+    real and the imaginary scalar of a frequency (shared = True).
+    mode 2 (the other outlier families): sigma_out = 0.05 raw, raw ~ exponential(so_lambda) per stacked row: y ~ exponential
+    of scale s = 0.05 / so_lambda, E[y^2] = 2 s^2, shared = False.
+
+    The rule is the trapezoid rule on a uniform grid in u = ln(y / s) of the given step, w_j = step y_j p(y_j) (halved at the
+    two ends); in u the integrand is analytic in a strip and decays at least exponentially both ways, so the rule converges
+    geometrically in 1 / step.  The grid starts at u = -36, below which lies a mass of so_alpha e^-36 (mode 2: e^-72 / 2).  It
+    ends, mode 2, at u = 5 (a mass of e^-148 beyond) and, mode 1, where the mass beyond, e^(-so_alpha u), is below 1e-14 and,
+    for so_alpha > 2, the part of E[y^2] beyond, so_alpha (so_alpha - 1) / 2 e^(-(so_alpha - 2) u) of it, is below 1e-11 --
+    but at u = 10 at the earliest and at u = 27.5 at the latest, which keeps Q <= 512 at the default step: so_alpha >= 1.2
+    meets the first and so_alpha >= 2.95 the second; a heavier tail is cut at u = 27.5 and the sums carry what that leaves
+    out (E[y^2] is returned in closed form either way).  DESIGN.md 3.5h has the measured accuracy."""
+    mode, lam, alpha, beta, h = int(mode), float(so_lambda), float(so_alpha), float(so_beta), float(step)
+    if mode not in (1, 2):
+        raise ValueError('sigma_out_table: no outlier error model (outlier_mode %d)' % mode)
+    if not (lam > 0 and np.isfinite(lam)) or not (h > 0) or (mode == 1 and not (alpha > 0 and beta > 0 and np.isfinite(alpha * beta))):
+        raise ValueError('sigma_out_table: the hyper-parameters and the step must be positive finite numbers')
+    lo = -36.0
+    if mode == 1:
+        s = 0.05 * beta / lam
+        hi = max(10.0, np.log(1e14) / alpha)
+        if alpha > 2:
+            hi = max(hi, (np.log(1e11) + np.log(alpha * (alpha - 1) / 2)) / (alpha - 2))
+        hi = min(hi, 27.5)
+        ey2 = 2 * s * s / ((alpha - 1) * (alpha - 2)) if alpha > 2 else np.inf
+    else:
+        s, hi = 0.05 / lam, 5.0
+        ey2 = 2 * s * s
+    u = lo + h * np.arange(int(np.ceil((hi - lo) / h)) + 1)
+    t = np.exp(u)
+    if mode == 1:
+        w = h * np.exp((np.log(alpha) + u) - (alpha + 1) * np.log1p(t))     # y p(y) = alpha t (1 + t)^-(alpha + 1), t = y / s
+    else:
+        w = h * np.exp(u - t)                                               # y p(y) = t exp(-t)
+    w[0] *= 0.5
+    w[-1] *= 0.5
+    return s * t, w, float(ey2), mode == 1
+
+
+MIX_MAX_NODES = 512                              # bdrt_heldout_mix_max_nodes()
+
+
+def sigma_out_prior_table(problem):
+    """`sigma_out_table` of a problem's outlier error model -- (y [Q], w [Q], E[y^2], shared), Q <= 512 -- from its
+    outlier_mode, so_lambda, so_alpha and so_beta alone.  Pure numpy: no GPU.  ValueError for a problem without an outlier model."""
+    mode = _outlier_mode(problem)
+    if mode not in (1, 2):
+        raise ValueError('sigma_out_prior_table: the problem has no outlier error model')
+    d = problem.dat
+    y, w, ey2, shared = sigma_out_table(mode, d.so_lambda, d.so_alpha, d.so_beta)
+    assert len(y) <= MIX_MAX_NODES
+    return y, w, ey2, shared
+
+
+def _heldout_grid(problem, freq_test, A_test_blocks, who, sigma_out=None):
     """Checks of the held-out grid that need no GPU -> (freq [H], the prediction rows packed as bdrt_heldout_transformed takes
-    them).  A_test_blocks: per block of the problem (A_re, A_im), each [H, K_b], or the two stacked, [2 H, K_b]."""
-    if int(getattr(getattr(problem, 'dat', None), 'outlier_mode', 0)):
-        raise NotImplementedError('%s: %s' % (who, OUTLIER_REFUSAL))
+    them).  A_test_blocks: per block of the problem (A_re, A_im), each [H, K_b], or the two stacked, [2 H, K_b].  sigma_out:
+    `check_sigma_out`; None refuses an outlier error model, 'prior' a problem without one."""
+    if check_sigma_out(sigma_out, who) is None:
+        if _outlier_mode(problem):
+            raise NotImplementedError('%s: %s' % (who, OUTLIER_REFUSAL))
+    elif not _outlier_mode(problem):
+        raise ValueError("%s: sigma_out='prior' needs an outlier error model; this problem has none" % who)
     freq = np.ascontiguousarray(np.asarray(freq_test, dtype=float).reshape(-1))
     H = len(freq)
     if H < 1 or not np.all(np.isfinite(freq) & (freq > 0)):
@@ -306,22 +385,70 @@ def _heldout_draw_count(S, who):
         raise ValueError('%s: %d draws per unit, the kernel holds at most %d' % (who, S, max_draws()))
 
 
-def heldout_transformed(problem, params, freq_test, A_test_blocks):
+def heldout_transformed(problem, params, freq_test, A_test_blocks, sigma_out=None):
     """Z_hat and sigma_tot [B, 2 H] (real halves, then imaginary halves) of B rows of CONSTRAINED parameters -- params [B, D]
     as `Problem.transformed` returns them -- at the frequencies freq_test [H], which need not be on the problem's grid, on the
     GPU (bdrt_heldout_transformed).  A_test_blocks: the prediction rows, per block (A_re, A_im) [H, K_b] each or stacked
     [2 H, K_b].  Block flags, x_scale, induc_scale and sigma_min are the problem's.  A row's result does not depend on what
-    else is in the call.  NotImplementedError for an outlier error model."""
+    else is in the call.  NotImplementedError for an outlier error model, unless sigma_out='prior': the second array is then the
+    base scale, sigma_tot without sigma_out (bdrt_heldout_mix_transformed), which `heldout_mix_reduce` integrates over its prior;
+    ValueError with 'prior' and no outlier model."""
     who = 'heldout_transformed'
-    freq, A = _heldout_grid(problem, freq_test, A_test_blocks, who)
+    freq, A = _heldout_grid(problem, freq_test, A_test_blocks, who, sigma_out)
     params = np.atleast_2d(_lib.f64(params))
     if params.ndim != 2 or params.shape[1] != problem.D:
         raise ValueError('%s: params must be [B, %d], not %s' % (who, problem.D, params.shape))
     B, H = params.shape[0], len(freq)
     Zh, sg = np.empty((B, 2 * H)), np.empty((B, 2 * H))
-    _lib.check(problem._lib.bdrt_heldout_transformed(problem.handle, _lib.ptr(params), B, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(Zh),
-                                                     _lib.ptr(sg)), 'bdrt_heldout_transformed')
+    name = 'bdrt_heldout_transformed' if sigma_out is None else 'bdrt_heldout_mix_transformed'
+    _lib.check(getattr(problem._lib, name)(problem.handle, _lib.ptr(params), B, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(Zh),
+                                           _lib.ptr(sg)), name)
     return Zh, sg
+
+
+def _mix_table(table, who):
+    """(y, w, E[y^2], shared) of `sigma_out_prior_table`, checked without a GPU -> contiguous arrays and plain numbers"""
+    try:
+        y, w, ey2, shared = table
+    except (TypeError, ValueError):
+        raise ValueError('%s: the table must be (y [Q], w [Q], E[y^2], shared)' % who) from None
+    y, w, ey2 = _lib.f64(y).reshape(-1), _lib.f64(w).reshape(-1), float(ey2)
+    if len(y) < 1 or len(y) != len(w) or not np.all(np.isfinite(y) & (y >= 0) & np.isfinite(w) & (w >= 0)) or not ey2 >= 0:
+        raise ValueError('%s: the table needs Q >= 1 nodes y >= 0 with weights w >= 0 and E[y^2] >= 0' % who)
+    if len(y) > MIX_MAX_NODES:
+        raise ValueError('%s: a table of %d nodes, the kernel holds at most %d' % (who, len(y), MIX_MAX_NODES))
+    return y, w, ey2, int(bool(shared))
+
+
+def heldout_mix_reduce(Zhat, sig_base, z, table, unit='frequency'):
+    """`heldout_reduce` under an outlier error model, on the GPU (bdrt_heldout_mix_reduce): sig_base is sigma_tot without
+    sigma_out (`heldout_transformed(..., sigma_out='prior')`) and table = (y, w, E[y^2], shared) its prior as an integration rule
+    (`sigma_out_prior_table`).  Per draw the density of a scalar is sum_j w_j N(z | Zhat, sig_base^2 + y_j^2); a frequency takes
+    the product of its two normals under one sum (shared) or the product of the two sums; lpd is the log of the draws' mean
+    density, mean is `heldout_reduce`'s, sd^2 gains E[y^2], pit is the mean of sum_j w_j Phi.  Definitions:
+    tests/heldout_mix_numpy.py.  Same shapes and NaN rule as `heldout_reduce`."""
+    who = 'heldout_mix_reduce'
+    pair = _pair(unit)
+    y, w, ey2, shared = _mix_table(table, who)
+    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig_base), _lib.f64(z)
+    one = Zhat.ndim == 2
+    if one:
+        Zhat, sig, z = Zhat[None], sig[None], z[None]
+    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
+        raise ValueError('%s: shapes %s, %s, %s do not fit' % (who, Zhat.shape, sig.shape, z.shape))
+    G, S, N2 = Zhat.shape
+    if pair and N2 % 2:
+        raise ValueError("%s: unit='frequency' needs an even number of columns, not %d" % (who, N2))
+    if G < 1 or N2 < 1:
+        raise ValueError('%s: empty input' % who)
+    _heldout_draw_count(S, who)
+    lib = _lib.require_gpu()
+    lpd = np.empty((G, N2 // 2 if pair else N2))
+    outs = [np.empty((G, N2)) for _ in HELDOUT_FIELDS]
+    _lib.check(lib.bdrt_heldout_mix_reduce(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, shared, _lib.ptr(y), _lib.ptr(w),
+                                           len(y), ey2, _lib.ptr(lpd), *[_lib.ptr(o) for o in outs]), 'bdrt_heldout_mix_reduce')
+    res = dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
+    return {key: v[0] for key, v in res.items()} if one else res
 
 
 def heldout_reduce(Zhat, sig, z, unit='frequency'):
@@ -359,15 +486,16 @@ def _heldout_part(unit, part, H, who):
 
 
 def sampler_heldout(sampler, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both',
-                    chunk_bytes=None):
+                    chunk_bytes=None, sigma_out=None):
     """`heldout_reduce(heldout_transformed(...))` of the draws a sampler holds in HBM (bdrt_sampler_heldout): units
     [unit_lo, unit_hi) in groups of `chains` consecutive units that sampled one spectrum, against z_test [G, 2 H] (or [2 H] for
     one group), the held-out data on each group's scale.  Per chunk of groups the batch evaluator gives the constrained
     parameters of the rows, and nothing but the per-unit results comes back.  part: 'both', or 'real' / 'imag' for that half
     of the scalars (units are points then).  Returns `heldout_reduce`'s dict, lpd [G, units], the others [G, columns of the
-    part]; every entry equals `host_heldout` on the downloaded draws bit for bit."""
+    part]; every entry equals `host_heldout` on the downloaded draws bit for bit.  sigma_out='prior': the same for an outlier
+    error model, with `heldout_mix_reduce` on the problem's `sigma_out_prior_table` (bdrt_sampler_heldout_mix)."""
     who = 'heldout'
-    freq, A = _heldout_grid(sampler.problem, freq_test, A_test_blocks, who)
+    freq, A = _heldout_grid(sampler.problem, freq_test, A_test_blocks, who, sigma_out)
     H = len(freq)
     pair, col0, ncols = _heldout_part(unit, part, H, who)
     chains, unit_lo, unit_hi = int(chains), int(unit_lo), int(unit_hi)
@@ -383,18 +511,22 @@ def sampler_heldout(sampler, unit_lo, unit_hi, chains, freq_test, A_test_blocks,
     _heldout_draw_count(chains * sampler.n_draws, who)
     lpd = np.empty((G, ncols // 2 if pair else ncols))
     outs = [np.empty((G, ncols)) for _ in HELDOUT_FIELDS]
-    _lib.check(sampler._lib.bdrt_sampler_heldout(sampler.handle, unit_lo, unit_hi, chains, pair, col0, ncols,
-                                                 chunk, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(z),
-                                                 _lib.ptr(lpd), *[_lib.ptr(o) for o in outs]), 'bdrt_sampler_heldout')
+    front = (sampler.handle, unit_lo, unit_hi, chains, pair, col0, ncols, chunk, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(z))
+    if sigma_out is None:
+        _lib.check(sampler._lib.bdrt_sampler_heldout(*front, _lib.ptr(lpd), *[_lib.ptr(o) for o in outs]), 'bdrt_sampler_heldout')
+    else:
+        y, w, ey2, shared = _mix_table(sigma_out_prior_table(sampler.problem), who)
+        _lib.check(sampler._lib.bdrt_sampler_heldout_mix(*front, shared, _lib.ptr(y), _lib.ptr(w), len(y), ey2, _lib.ptr(lpd),
+                                                         *[_lib.ptr(o) for o in outs]), 'bdrt_sampler_heldout_mix')
     return dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
 
 
-def host_heldout(problem, draws, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both'):
+def host_heldout(problem, draws, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both', sigma_out=None):
     """What `sampler_heldout` computes, on host-resident unconstrained draws [G, chains * n_draws, D] through the host-staged
     entry points (`Problem.transformed` for the constrained parameters, `heldout_transformed`, `heldout_reduce`): the yardstick
-    of the device path."""
+    of the device path.  sigma_out='prior': through `heldout_transformed(..., sigma_out='prior')` and `heldout_mix_reduce`."""
     who = 'heldout'
-    freq, _ = _heldout_grid(problem, freq_test, A_test_blocks, who)
+    freq, _ = _heldout_grid(problem, freq_test, A_test_blocks, who, sigma_out)
     H = len(freq)
     _, col0, ncols = _heldout_part(unit, part, H, who)
     draws, z = np.asarray(draws, dtype=float), np.atleast_2d(np.asarray(z_test, dtype=float))
@@ -402,9 +534,12 @@ def host_heldout(problem, draws, chains, freq_test, A_test_blocks, z_test, unit=
         raise ValueError('%s: draws must be [G, S, %d] and z_test [G, %d]' % (who, problem.D, 2 * H))
     _heldout_draw_count(draws.shape[1], who)
     cols = slice(col0, col0 + ncols)
-    tr = [heldout_transformed(problem, problem.transformed(d)[0], freq, A_test_blocks) for d in draws]
-    return heldout_reduce(np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
-                          np.ascontiguousarray(np.stack([t[1] for t in tr])[:, :, cols]), np.ascontiguousarray(z[:, cols]), unit)
+    tr = [heldout_transformed(problem, problem.transformed(d)[0], freq, A_test_blocks, sigma_out) for d in draws]
+    arrays = (np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
+              np.ascontiguousarray(np.stack([t[1] for t in tr])[:, :, cols]), np.ascontiguousarray(z[:, cols]))
+    if sigma_out is None:
+        return heldout_reduce(*arrays, unit)
+    return heldout_mix_reduce(*arrays, sigma_out_prior_table(problem), unit)
 
 
 def _host_arrays(problem, draws, z, part):
@@ -637,12 +772,14 @@ def loo_predict_many(fits, zs, chains=None, unit='frequency', reff='auto', colum
     return out
 
 # ---------------------------------------------------------------------------------------------------- K-fold and exact refits
-def heldout_result(p, z, frequencies, part, unit, S, z_scale):
+def heldout_result(p, z, frequencies, part, unit, S, z_scale, sigma_out=None):
     """One group's row of `heldout_reduce`'s dict (lpd [units], mean, sd, pit [columns of the part]) against the scaled held-out
     data z [columns of the part] -> LooResult in the units of the impedance as supplied: frequencies, elpd (the sum), elpd_i per
     unit (log(z_scale) subtracted once per scalar), Z_pred (complex), sigma_pred_re/_im, pit_re/_im, resid_re/_im, n_draws.
-    part 'real' / 'imag': the other half is NaN and units are points."""
+    part 'real' / 'imag': the other half is NaN and units are points.  sigma_out='prior' (p from `heldout_mix_reduce`) is
+    recorded under that key; None adds no key."""
     pair, _ = check_device_args(unit, part, None, 'heldout')
+    check_sigma_out(sigma_out, 'heldout_result')
     freq = np.array(frequencies, dtype=float).reshape(-1)
     H, sc = len(freq), float(z_scale)
     half = {'real': ('re',), 'imag': ('im',), 'both': ('re', 'im')}[part]
@@ -663,6 +800,8 @@ def heldout_result(p, z, frequencies, part, unit, S, z_scale):
     out['Z_pred'].real, out['Z_pred'].imag = m['re'] * sc, m['im'] * sc
     for h in ('re', 'im'):
         out['sigma_pred_' + h], out['pit_' + h], out['resid_' + h] = sd[h] * sc, pit[h], rs[h]
+    if sigma_out is not None:
+        out['sigma_out'] = sigma_out
     return out
 
 
@@ -698,7 +837,8 @@ def kfold_result(labels, fold_results, unit='frequency', part='both'):
     """The `heldout_result`s of the folds of ONE spectrum -> its K-fold LooResult, in the order of the supplied grid.
     labels [n]: `fold_labels`; fold_results {label: heldout_result of the frequencies with that label, in grid order}.
     Carries what `compare` reads -- elpd_loo (the sum of the folds' elpd_i), se, elpd_i, n_units; p_loo NaN, pareto_k all NaN,
-    n_bad_k 0 --, method='kfold', the `fold` of every unit and the predictive arrays of `heldout_result`."""
+    n_bad_k 0 --, method='kfold', the `fold` of every unit and the predictive arrays of `heldout_result`; and `sigma_out` when
+    the folds carry it (all of them, or none)."""
     pair, _ = check_device_args(unit, part, None, 'kfold')
     labels = np.asarray(labels, dtype=int)
     n = len(labels)
@@ -728,6 +868,11 @@ def kfold_result(labels, fold_results, unit='frequency', part='both'):
         n_draws = int(r['n_draws']) if n_draws is None else min(n_draws, int(r['n_draws']))
     if not np.all(filled == 1):
         raise ValueError('kfold_result: every frequency must be held out exactly once')
+    modes = {r.get('sigma_out') for r in fold_results.values()}
+    if len(modes) > 1:
+        raise ValueError('kfold_result: the folds differ in sigma_out (%s)' % sorted(map(repr, modes)))
+    if modes != {None}:
+        arrays = dict(arrays, sigma_out=modes.pop())
     return LooResult(elpd_loo=float(np.sum(elpd_i)), se=float(np.sqrt(n_units * np.var(elpd_i))), p_loo=float('nan'),
                      n_units=int(n_units), n_draws=n_draws, elpd_i=elpd_i, pareto_k=np.full(n_units, np.nan), n_bad_k=0,
                      method='kfold', fold=np.concatenate([labels, labels]) if both_points else labels.copy(), frequencies=freq,

@@ -429,6 +429,31 @@ int bdrt_heldout_reduce(const double *Zhat, const double *sig, const double *z, 
 int bdrt_sampler_heldout(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
                          size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, double *lpd,
                          double *mean, double *sd, double *pit);
+/* ---- (4c) held-out frequencies under the outlier error models: sigma_out integrated over its prior -----
+ * Definitions: tests/heldout_mix_numpy.py.  The prior of sigma_out is fixed by data, so the predictive of a frequency the fit has
+ * not seen is the draw's normal with sigma_out integrated over that prior.  The integral is a table the caller supplies: nodes
+ * y [Q] (>= 0) and weights w [Q] (>= 0, summing to 1) with sum_j w_j f(y_j) ~ E f(sigma_out), 1 <= Q <= bdrt_heldout_mix_max_nodes()
+ * (-2 above), and ey2 = E[sigma_out^2] (+inf allowed).  shared = 1: the real and the imaginary scalar of a frequency have one
+ * sigma_out (outlier_mode 1); 0: one each (outlier_mode 2).  The entries of (4b) keep refusing these models.
+ *
+ * bdrt_heldout_transformed for a problem WITH an outlier model (-2 without one): sigma_base is sigma_tot without sigma_out. */
+int bdrt_heldout_mix_max_nodes(void);
+int bdrt_heldout_mix_transformed(bdrt_problem *p, const double *params, int B, const double *freq_test, int H, const double *A_test,
+                                 double *Z_hat, double *sigma_base);
+/* Zhat, sig_base [G][S][N2], z [G][N2] as in bdrt_heldout_reduce.  Per draw s and scalar, with v_j = sig_base^2 + y_j^2:
+ * m_s = sum_j w_j N(z | Zhat, v_j); a pair unit takes the product of the two normals under one sum (shared) or the product of the
+ * two sums; lpd [G][U] = log(mean_s m_s), formed from log m_s so that no residual underflows it; mean [G][N2] as in
+ * bdrt_heldout_reduce; sd^2 = that entry's sd^2 + ey2; pit = mean_s sum_j w_j Phi((z - Zhat) / sqrt(v_j)), per scalar.  With the
+ * table Q = 1, y = 0, w = 1, ey2 = 0 mean, sd and pit have bdrt_heldout_reduce's bits and lpd agrees to rounding.  A unit's
+ * result depends on its own rows, S and the table only.  A unit with a non-finite term gives NaN, that unit only.
+ * 2 <= S <= bdrt_psis_loo_max_draws() (-2 above). */
+int bdrt_heldout_mix_reduce(const double *Zhat, const double *sig_base, const double *z, int G, int S, int N2, int pair, int shared,
+                            const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit);
+/* Both on the draws a sampler holds, chunked by groups exactly as bdrt_sampler_heldout; each output equals the two host-staged
+ * entries on the downloaded draws bit for bit.  -2 for a problem without an outlier model. */
+int bdrt_sampler_heldout_mix(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
+                             size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, int shared,
+                             const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
