@@ -426,14 +426,14 @@ class StanModel:
             init_theta = self._init_theta(init, chains, seed)
         res = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
                            chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo, heldout=heldout)
-        draws, lp, diag = res[:3]
+        draws, lp, diag = res
         theta = draws.reshape(chains * n_draws, P.D)
         fit = StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
                       control=dict(adapt_delta=ctrl.adapt_delta, max_treedepth=ctrl.max_treedepth), warmup=warmup)
         if loo is not None:
-            fit.device_loo = res[3]
+            fit.device_loo = res.loo
         if heldout is not None:
-            fit.device_heldout = res[-1]
+            fit.device_heldout = res.heldout
         return fit
 
 
@@ -587,54 +587,46 @@ class Sampler:
         return mean, pct
 
 
+class SampleResult(tuple):
+    """What `sample_units` returns: always the tuple (draws, lp, diag); what was reduced while the sampler held the draws is
+    under the attributes `diagnostics`, `loo` and `heldout`, None when not asked for."""
+
+    def __new__(cls, draws, lp, diag, diagnostics=None, loo=None, heldout=None):
+        self = super().__new__(cls, (draws, lp, diag))
+        self.diagnostics, self.loo, self.heldout = diagnostics, loo, heldout
+        return self
+
+
 def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, chain_ids=None, init_theta=None,
                  rounds_per_launch=None, diagnostics_chains=None, loo=None, heldout=None):
     """Run n_units chains (unit u: spectrum spec[u], RNG stream (seed, chain_ids[u])) to completion on the GPU.
-    Returns draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain diagnostics.
+    Returns a `SampleResult`: the tuple (draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain
+    diagnostics), always of length 3, with the attributes below, each None unless asked for.
     diagnostics_chains=M: also reduce the convergence diagnostics of the constrained parameters, groups of M consecutive units,
-    in one launch while the sampler still holds the draws; a fourth item (mean, sd, n_eff, Rhat), each [n_units / M, D].
+    in one launch while the sampler still holds the draws; `.diagnostics` is (mean, sd, n_eff, Rhat), each [n_units / M, D].
     loo=dict(chains=M, loo=True, predict=False, unit=, part=, reff=, chunk_bytes=): also reduce PSIS-LOO (`Sampler.loo`) and / or
-    the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; one more item, a dict
-    with the entries 'loo' and / or 'predict'.
+    the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; `.loo` is a dict with the
+    entries 'loo' and / or 'predict'.
     heldout=dict(chains=M, freq_test=, A_test_blocks=, z_test=, unit=, part=, chunk_bytes=, sigma_out=): also reduce the predictive of
-    held-out frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; one more item (the last), its dict."""
-    hkw = None
-    if heldout is not None:
-        hkw = dict(heldout)
-        need = {'chains', 'freq_test', 'A_test_blocks', 'z_test'}
-        unknown = sorted(set(hkw) - need - {'unit', 'part', 'chunk_bytes', 'sigma_out'})
-        if unknown or not need <= set(hkw):
-            raise ValueError('sample_units: heldout needs chains, freq_test, A_test_blocks, z_test and takes unit, part, chunk_bytes, '
-                             'sigma_out (got %s)' % sorted(hkw))
-        from .loo import _heldout_grid, _heldout_part
-        f_, _ = _heldout_grid(problem, hkw['freq_test'], hkw['A_test_blocks'], 'heldout', hkw.get('sigma_out'))
-        _heldout_part(hkw.get('unit', 'frequency'), hkw.get('part', 'both'), len(f_), 'heldout')
-    kw = None
-    if loo is not None:
-        kw = dict(loo)
-        unknown = sorted(set(kw) - {'chains', 'loo', 'predict', 'unit', 'part', 'reff', 'chunk_bytes'})
-        if unknown or 'chains' not in kw:
-            raise ValueError('sample_units: loo needs chains and takes loo, predict, unit, part, reff, chunk_bytes (got %s)' % sorted(kw))
-        from .loo import check_device_args
-        check_device_args(kw.get('unit', 'frequency'), kw.get('part', 'both'), kw.get('reff', 'auto'))
+    held-out frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; `.heldout` is its dict."""
+    from .loo import heldout_request, loo_request
+    hkw = None if heldout is None else heldout_request(heldout, problem, 'sample_units')
+    kw = None if loo is None else loo_request(loo, 'sample_units', need_chains=True)
     with Sampler(problem, n_units, warmup, n_draws, seed, ctrl, spec=spec, chain_ids=chain_ids, init_theta=init_theta) as smp:
         smp.run(rounds_per_launch)
-        res = smp.results()
+        res = SampleResult(*smp.results())
         if diagnostics_chains:
-            res = res + (smp.diagnostics(0, n_units, diagnostics_chains),)
+            res.diagnostics = smp.diagnostics(0, n_units, diagnostics_chains)
         if kw is not None:
-            args = (0, n_units, kw['chains'], kw.get('unit', 'frequency'), kw.get('part', 'both'), kw.get('reff', 'auto'),
-                    kw.get('chunk_bytes'))
-            out = {}
-            if kw.get('loo', True):
-                out['loo'] = smp.loo(*args)
-            if kw.get('predict', False):
-                out['predict'] = smp.loo_predict(*args)
-            res = res + (out,)
+            args = (0, n_units, kw['chains'], kw['unit'], kw['part'], kw['reff'], kw['chunk_bytes'])
+            res.loo = {}
+            if kw['loo']:
+                res.loo['loo'] = smp.loo(*args)
+            if kw['predict']:
+                res.loo['predict'] = smp.loo_predict(*args)
         if hkw is not None:
-            res = res + (smp.heldout(0, n_units, hkw['chains'], hkw['freq_test'], hkw['A_test_blocks'], hkw['z_test'],
-                                     hkw.get('unit', 'frequency'), hkw.get('part', 'both'), hkw.get('chunk_bytes'),
-                                     hkw.get('sigma_out')),)
+            res.heldout = smp.heldout(0, n_units, hkw['chains'], hkw['freq_test'], hkw['A_test_blocks'], hkw['z_test'],
+                                      hkw['unit'], hkw['part'], hkw['chunk_bytes'], hkw['sigma_out'])
         return res
 
 

@@ -1132,18 +1132,12 @@ class Inverter:
         order = {}
         for i, job in enumerate(jobs):
             order.setdefault(self._batch_key(job), []).append(i)
-        if hkw is not None:                                                  # (batches that only `_batch_jobs` could tell: before the first is sampled)
-            for idx in order.values():
-                f0 = hkw['pairs'][idx[0]][0]
-                if any(not np.array_equal(hkw['pairs'][i][0], f0) for i in idx[1:]):
-                    raise ValueError('heldout: the spectra of one batch must share f_test (spectra %s)' % idx)
-                if hkw['sigma_out'] is None and any(jobs[i]['outliers'] for i in idx):
-                    from . import loo as _loo
-                    raise NotImplementedError('fit_many(heldout=...): ' + _loo.OUTLIER_REFUSAL)
-        for idx in order.values():
-            self._fit_batch([views[i] for i in idx], [jobs[i] for i in idx], mode, random_seed, max_iter, warmup, samples,
-                            chains, algorithm, group, check_diagnostics, idx, lkw,
-                            None if hkw is None else dict(hkw, pairs=[hkw['pairs'][i] for i in idx], part=part))
+        batches = [([views[i] for i in idx], [jobs[i] for i in idx], idx) for idx in order.values()]
+        # (every batch's held-out request before the first is sampled: it refuses what only `_batch_jobs` could tell)
+        held = [None if hkw is None else self._heldout_job(v, j, dict(hkw, pairs=[hkw['pairs'][i] for i in idx]), part, chains)
+                for v, j, idx in batches]
+        for (v, j, idx), h in zip(batches, held):
+            self._fit_batch(v, j, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics, idx, lkw, h)
         for inv, job in zip(views, jobs):
             inv._fit_finish(job, mode, job['sigma_min'], check_outliers)
         return views
@@ -1180,7 +1174,8 @@ class Inverter:
                 self._loo_unit_part = (lkw['unit'], part)
             if 'predict' in res:
                 p = {k: v[g] for k, v in res['predict'].items()}
-                zc = z if part == 'both' else (z[:nf] if part == 'real' else z[nf:])
+                col0, ncols = _loo.part_columns(part, nf)
+                zc = z[col0:col0 + ncols]
                 self.loo_predict_result = self._loo_predict_view(_loo._predict_result(p, zc, S, freq, prefix), part, freq)
         finally:
             _loo.logger.disabled = was
@@ -1215,8 +1210,9 @@ class Inverter:
                 raise NotImplementedError('fit_many(heldout=...) is not available inside a process group with more than one rank')
         except ImportError:
             pass
-        _loo.check_device_args('point' if part != 'both' else unit, part, None, 'heldout')
         _loo._pair(unit)
+        unit = _loo.effective_unit(unit, part)
+        _loo.check_device_args(unit, part, None, 'heldout')
 
         def is_pair(h):
             """(f_test, Z_test): two one-dimensional arrays or sequences of numbers"""
@@ -1240,16 +1236,14 @@ class Inverter:
                 raise ValueError('heldout: f_test and Z_test must have the same length, at least 1')
             _validate_spectrum(f, Z)
             out.append((f, Z))
-        return dict(pairs=out, unit='point' if part != 'both' else unit, sigma_out=sigma_out)
+        return dict(pairs=out, unit=unit, sigma_out=sigma_out)
 
     @classmethod
     def _heldout_shared_grids(cls, hkw, frequencies, n, options):
         """Spectra that will share a batch -- one training grid, equal per-spectrum options -- must share f_test: refused here,
         before any matrix is built or any batch sampled.  (Grids that differ in their last bits only, and outliers='auto', are
         told apart by `_batch_jobs`; `fit_many` looks again behind it.)"""
-        per_grid = (isinstance(frequencies, (list, tuple)) and n > 0 and len(frequencies) == n and
-                    all(np.ndim(f) == 1 for f in frequencies)) or (isinstance(frequencies, np.ndarray) and frequencies.ndim == 2)
-        grids = list(frequencies) if per_grid else [frequencies] * n
+        grids = list(frequencies) if cls._per_grid(frequencies, n) else [frequencies] * n
         opts = [cls._per_spectrum(v, n, 'option') for v in options]
         seen = {}
         for i in range(n):
@@ -1273,37 +1267,46 @@ class Inverter:
         `_get_prediction_matrices`, and the held-out data of every spectrum on that spectrum's own scale (`scale_Z` has seen the
         training rows only)."""
         from . import loo as _loo
-        with_outliers = [bool(job['outliers']) for job in jobs]
-        if hkw.get('sigma_out') is None and any(with_outliers):
-            raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
-        if any(with_outliers) != all(with_outliers):
-            raise ValueError('heldout: the spectra of one batch must share the error model')
         f0 = hkw['pairs'][0][0]
         if any(len(f) != len(f0) or not np.array_equal(f, f0) for f, _ in hkw['pairs'][1:]):
             raise ValueError('heldout: the spectra of one batch must share f_test')
+        with_outliers = [bool(job['outliers']) for job in jobs]
+        if hkw['sigma_out'] is None and any(with_outliers):
+            raise NotImplementedError('fit(heldout=...): ' + _loo.OUTLIER_REFUSAL)
+        if any(with_outliers) != all(with_outliers):
+            raise ValueError('heldout: the spectra of one batch must share the error model')
         keep_re, keep_im = float(part != 'imag'), float(part != 'real')
         names = views[0]._block_distributions(jobs[0]['model_type'])
         pm = views[0]._get_prediction_matrices(f0, names)
         A = [np.concatenate((keep_re * pm[n]['A_re'], keep_im * pm[n]['A_im'])) for n in names]
         z = np.vstack([np.concatenate((keep_re * Z.real, keep_im * Z.imag)) / inv._Z_scale for inv, (_, Z) in zip(views, hkw['pairs'])])
-        held = dict(chains=chains, freq_test=f0, A_test_blocks=A, z_test=z, unit=hkw['unit'], part=part)
-        if hkw.get('sigma_out') is not None and all(with_outliers):          # (outliers='auto' that chose the plain model: as without)
-            held['sigma_out'] = hkw['sigma_out']
-        return held
+        # (outliers='auto' that chose the plain model: as without sigma_out)
+        return dict(chains=chains, freq_test=f0, A_test_blocks=A, z_test=z, unit=hkw['unit'], part=part,
+                    sigma_out=hkw['sigma_out'] if all(with_outliers) else None)
 
     def _store_heldout(self, res, g, held, S):
         """Row g of `Sampler.heldout`'s dict -> `heldout_result`."""
         from . import loo as _loo
-        H, part = len(held['freq_test']), held['part']
-        cols = {'both': slice(0, 2 * H), 'real': slice(0, H), 'imag': slice(H, 2 * H)}[part]
-        self.heldout_result = _loo.heldout_result({k: v[g] for k, v in res.items()}, held['z_test'][g][cols], held['freq_test'], part,
-                                                  held['unit'], S, self._Z_scale, held.get('sigma_out'))
+        part = held['part']
+        col0, ncols = _loo.part_columns(part, len(held['freq_test']))
+        self.heldout_result = _loo.heldout_result({k: v[g] for k, v in res.items()}, held['z_test'][g][col0:col0 + ncols],
+                                                  held['freq_test'], part, held['unit'], S, self._Z_scale, held['sigma_out'])
 
     @staticmethod
     def _batch_key(job):
         """Spectra with equal keys share one problem in HBM: the model file, the frequency grid (hence, on this instance's basis,
         the matrices) and the options that enter the Stan data apart from 'Z' (`_stack_stan_data` verifies the entries)."""
         return job['batch_key']
+
+    @staticmethod
+    def _per_grid(frequencies, n):
+        """Whether `frequencies` holds one grid per spectrum -- a list of n one-dimensional grids, or a 2-d array of n rows --
+        rather than one grid for all."""
+        if isinstance(frequencies, np.ndarray) and frequencies.ndim == 2:
+            if len(frequencies) != n:
+                raise ValueError('fit_many: %d frequency grids for %d spectra' % (len(frequencies), n))
+            return True
+        return isinstance(frequencies, (list, tuple)) and n > 0 and len(frequencies) == n and all(np.ndim(f) == 1 for f in frequencies)
 
     @staticmethod
     def _per_spectrum(value, n, name, who='fit_many'):
@@ -1324,13 +1327,7 @@ class Inverter:
         import copy
         Z_list = [np.asarray(Z) for Z in Z_list]
         n = len(Z_list)
-        per_grid = isinstance(frequencies, (list, tuple)) and n > 0 and len(frequencies) == n and \
-            all(np.ndim(f) == 1 for f in frequencies)
-        if isinstance(frequencies, np.ndarray) and frequencies.ndim == 2:
-            per_grid = True
-            if len(frequencies) != n:
-                raise ValueError('fit_many: %d frequency grids for %d spectra' % (len(frequencies), n))
-        freqs = [np.asarray(f, dtype=float) for f in frequencies] if per_grid else [frequencies] * n
+        freqs = [np.asarray(f, dtype=float) for f in frequencies] if self._per_grid(frequencies, n) else [frequencies] * n
         opt = {k: self._per_spectrum(v, n, k) for k, v in (('sigma_min', sigma_min), ('nonneg', nonneg), ('outliers', outliers),
                                                           ('inductance_scale', inductance_scale),
                                                           ('outlier_lambda', outlier_lambda))}
@@ -1383,9 +1380,9 @@ class Inverter:
 
     @staticmethod
     def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics=False,
-                   index=None, lkw=None, hkw=None):
+                   index=None, lkw=None, held=None):
         """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view, with `lkw`
-        (`_loo_arguments`) `loo_result` / `loo_predict_result`, and with `hkw` (`_heldout_arguments`) `heldout_result`."""
+        (`_loo_arguments`) `loo_result` / `loo_predict_result`, and with `held` (`_heldout_job`) `heldout_result`."""
         import ctypes as C
         from . import engine, parallel
         from ._lib import NutsControl
@@ -1457,14 +1454,13 @@ class Inverter:
         from . import diagnostics
         flat = diagnostics.flat_parameter_count(jobs[0]['model_str'], dat)
         param_stats = None
-        held = None if hkw is None else Inverter._heldout_job(views, jobs, hkw, hkw['part'], chains)
         if world > 1:
             blocks, kw, _ = engine.blocks_from_dat(model.model_name, dat)
             pk = dict(kw, blocks=blocks, Z=np.asarray(dat['Z'], dtype=float), freq=np.asarray(dat['freq'], dtype=float))
             want = bool(check_diagnostics and flat <= diagnostics.MAX_FLAT)
             res = parallel.sample_sharded(pk if dist.get_rank(group) == 0 else None, ns, chains, warmup, n_draws, seed=random_seed,
                                           control=control, group=group, gather='draws', init_theta=init_theta, diagnostics=want,
-                                          loo=None if lkw is None else {k: v for k, v in lkw.items()})
+                                          loo=lkw)
             if want:
                 param_stats = (None, None, res['n_eff'], res['Rhat'])
             loo_res = {k2: res[k1] for k1, k2 in (('loo', 'loo'), ('loo_predict', 'predict')) if k1 in res}
@@ -1480,12 +1476,8 @@ class Inverter:
             res = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
                                       init_theta=init_theta, diagnostics_chains=want,
                                       loo=None if lkw is None else dict(lkw, chains=chains), heldout=held)
-            if held is not None:
-                res, held_res = res[:-1], res[-1]
-            draws, lp, diag = res[:3]
-            if want:
-                param_stats = res[3]
-            loo_res = res[-1] if lkw is not None else {}
+            draws, lp, diag = res
+            param_stats, loo_res, held_res = res.diagnostics, res.loo, res.heldout
         ctl = dict(adapt_delta=control['adapt_delta'], max_treedepth=control.get('max_treedepth', 10))
         for i, inv in enumerate(views):
             u0, u1 = i * chains, (i + 1) * chains
@@ -1973,9 +1965,10 @@ class Inverter:
     # ================================================================== model comparison (bayes_drt_amd.loo)
     def _loo_job(self, part):
         """(fit, scaled data [2 Nf], columns, frequencies) of this instance's sampling fit for `loo`."""
+        from . import loo as _loo
         if self.fit_type != 'bayes':
             raise ValueError('LOO model comparison is only available for bayes_fit')
-        if part not in ('both', 'real', 'imag'):
+        if part not in _loo.PARTS:
             raise ValueError("part must be 'both', 'real' or 'imag'")
         dat = getattr(self, '_stan_input', None)
         if dat is not None and 'Z' in dat:
@@ -1983,8 +1976,8 @@ class Inverter:
         else:
             Zs = np.asarray(self.Z_train) / self._Z_scale
             z = np.concatenate((Zs.real, Zs.imag))
-        nf = len(z) // 2
-        columns = None if part == 'both' else (slice(0, nf) if part == 'real' else slice(nf, 2 * nf))
+        col0, ncols = _loo.part_columns(part, len(z) // 2)
+        columns = None if part == 'both' else slice(col0, col0 + ncols)
         freq = dat['freq'] if dat is not None and 'freq' in dat else self.f_train
         return self._sample_result, z, columns, np.asarray(freq, dtype=float)
 
@@ -2001,7 +1994,7 @@ class Inverter:
         fit, z, columns, freq = self._loo_job(part)
         self.loo_result = _loo.loo(fit, z, unit=unit, reff=reff, log_scale=float(np.log(self._Z_scale)), columns=columns,
                                    frequencies=freq)
-        self._loo_unit_part = ('point' if part != 'both' else unit, part)        # (what `reloo` asks of the result it repairs)
+        self._loo_unit_part = (_loo.effective_unit(unit, part), part)           # (what `reloo` asks of the result it repairs)
         return self.loo_result
 
     @staticmethod
@@ -2019,7 +2012,7 @@ class Inverter:
                             chunk_bytes=chunk_bytes or _loo.CHUNK_BYTES)
         for inv, r in zip(inverters, res):
             inv.loo_result = r
-            inv._loo_unit_part = ('point' if part != 'both' else unit, part)
+            inv._loo_unit_part = (_loo.effective_unit(unit, part), part)
         return res
 
     def _loo_predict_view(self, r, part, freq):
@@ -2126,6 +2119,7 @@ class Inverter:
         if sigma_out is not None:
             kw['heldout_sigma_out'] = sigma_out
         kw.setdefault('check_outliers', False)
+        kw.setdefault('part', 'both')
         return kw
 
     def kfold_many(self, frequencies, Z_list, folds=10, unit='frequency', sigma_out=None, **fit_kw):
@@ -2152,8 +2146,8 @@ class Inverter:
             _validate_spectrum(f, Z)
         labels = _loo.fold_labels(f, folds)
         kw = self._refit_kw(fit_kw, 'kfold', sigma_out)
-        part = kw.get('part', 'both')
-        hunit = 'point' if part != 'both' else unit
+        part = kw['part']
+        hunit = _loo.effective_unit(unit, part)
         _loo.check_device_args(hunit, part, None, 'kfold')
         if not Z_list:
             return []
@@ -2201,7 +2195,7 @@ class Inverter:
             raise ValueError("reloo needs this instance's loo_result per frequency of the supplied grid: call "
                              "loo(unit='frequency', part='both') (or fit(..., loo=True)) first")
         kw = self._refit_kw(fit_kw, 'reloo', sigma_out)
-        if kw.get('part', 'both') != 'both':
+        if kw['part'] != 'both':
             raise ValueError("reloo needs unit='frequency', part='both': call loo(unit='frequency', part='both') first")
         cand = _loo.reloo_candidates(r, k_threshold, max_refits)
         order = np.argsort(f)[::-1]                                  # the order of the fit's rows, hence of loo_result's units

@@ -85,20 +85,27 @@ def _pair(unit):
 
 
 # ---------------------------------------------------------------------------------------------------- device reductions
-def pointwise_log_lik(Zhat, sig, z, unit='frequency'):
-    """Log-likelihood of `Z ~ normal(Z_hat, sigma_tot)` per draw and observation on the GPU: Zhat, sig [G, S, 2 Nf] and z
-    [G, 2 Nf] (or [S, 2 Nf] and [2 Nf]: G = 1) -> [G, S, Nf] (unit='frequency': real plus imaginary part) or [G, S, 2 Nf]
-    (unit='point').  A non-positive or non-finite sig gives NaN."""
+def _stacked(who, Zhat, sig, z, unit):
+    """Zhat, sig [G, S, N2] and z [G, N2] (or [S, N2] and [N2]: G = 1, `one`) as contiguous float64 arrays of three and two
+    dimensions -> (pair, Zhat, sig, z, one)."""
     pair = _pair(unit)
     Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
     one = Zhat.ndim == 2
     if one:
         Zhat, sig, z = Zhat[None], sig[None], z[None]
     if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
-        raise ValueError('pointwise_log_lik: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+        raise ValueError('%s: shapes %s, %s, %s do not fit' % (who, Zhat.shape, sig.shape, z.shape))
+    if pair and Zhat.shape[2] % 2:
+        raise ValueError("%s: unit='frequency' needs an even number of columns, not %d" % (who, Zhat.shape[2]))
+    return pair, Zhat, sig, z, one
+
+
+def pointwise_log_lik(Zhat, sig, z, unit='frequency'):
+    """Log-likelihood of `Z ~ normal(Z_hat, sigma_tot)` per draw and observation on the GPU: Zhat, sig [G, S, 2 Nf] and z
+    [G, 2 Nf] (or [S, 2 Nf] and [2 Nf]: G = 1) -> [G, S, Nf] (unit='frequency': real plus imaginary part) or [G, S, 2 Nf]
+    (unit='point').  A non-positive or non-finite sig gives NaN."""
+    pair, Zhat, sig, z, one = _stacked('pointwise_log_lik', Zhat, sig, z, unit)
     G, S, N2 = Zhat.shape
-    if pair and N2 % 2:
-        raise ValueError("pointwise_log_lik: unit='frequency' needs an even number of columns, not %d" % N2)
     lib = _lib.require_gpu()
     out = np.empty((G, S, N2 // 2 if pair else N2))
     _lib.check(lib.bdrt_pointwise_loglik(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, _lib.ptr(out)),
@@ -116,10 +123,7 @@ def psis_loo(ll, reff=None):
     if ll.ndim != 3:
         raise ValueError('psis_loo: ll must be [S, N] or [G, S, N]')
     G, S, N = ll.shape
-    if S > max_draws():
-        raise ValueError('psis_loo: %d draws per observation, the kernel holds at most %d' % (S, max_draws()))
-    if S < 2:
-        raise ValueError('psis_loo: at least 2 draws are needed')
+    _draw_count(S, 'psis_loo', max_draws, 'observation')
     r = None
     if reff is not None:
         r = _lib.f64(np.broadcast_to(np.asarray(reff, dtype=float), (G, N)))
@@ -143,20 +147,9 @@ def psis_predict(Zhat, sig, z, unit='frequency', reff=None):
     [2 Nf]: G = 1).  A unit is one frequency (real plus imaginary part left out together) or one point; reff: None (1), a
     number, or [G, units].  Returns a dict of mean, sd, pit (LOO) and mean_post, sd_post, pit_post (equal weights), each
     [G, 2 Nf], and pareto_k (float), n_tail (int) [G, units] -- those two equal `psis_loo(pointwise_log_lik(...), reff)`'s."""
-    pair = _pair(unit)
-    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
-    one = Zhat.ndim == 2
-    if one:
-        Zhat, sig, z = Zhat[None], sig[None], z[None]
-    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
-        raise ValueError('psis_predict: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
+    pair, Zhat, sig, z, one = _stacked('psis_predict', Zhat, sig, z, unit)
     G, S, N2 = Zhat.shape
-    if pair and N2 % 2:
-        raise ValueError("psis_predict: unit='frequency' needs an even number of columns, not %d" % N2)
-    if S > predict_max_draws():
-        raise ValueError('psis_predict: %d draws per unit, the kernel holds at most %d' % (S, predict_max_draws()))
-    if S < 2:
-        raise ValueError('psis_predict: at least 2 draws are needed')
+    _draw_count(S, 'psis_predict', predict_max_draws)
     U = N2 // 2 if pair else N2
     r = None
     if reff is not None:
@@ -174,7 +167,24 @@ def psis_predict(Zhat, sig, z, unit='frequency', reff=None):
 
 # ---------------------------------------------------------------------------------------------------- on a sampler's draws
 PARTS = ('both', 'real', 'imag')
-LOO_KW = ('unit', 'reff')                            # what `fit_many(loo_kw=...)` accepts
+# the `loo=` and `heldout=` requests of the engine: every key, with its default or among those that must be given
+LOO_DEFAULTS = dict(chains=None, loo=True, predict=False, unit='frequency', part='both', reff='auto', chunk_bytes=None)
+LOO_KEYS = tuple(LOO_DEFAULTS)
+LOO_KW = ('unit', 'reff')                            # what of it `fit_many(loo_kw=...)` accepts
+HELDOUT_NEEDS = ('chains', 'freq_test', 'A_test_blocks', 'z_test')
+HELDOUT_DEFAULTS = dict(unit='frequency', part='both', chunk_bytes=None, sigma_out=None)
+HELDOUT_KEYS = HELDOUT_NEEDS + tuple(HELDOUT_DEFAULTS)
+
+
+def effective_unit(unit, part):
+    """A fit (or a request) of one part has points for units."""
+    return 'point' if part != 'both' else unit
+
+
+def part_columns(part, n):
+    """(first column, number of columns) of a part among 2 n columns, real halves first; the slice is
+    slice(col0, col0 + ncols)."""
+    return {'both': (0, 2 * n), 'real': (0, n), 'imag': (n, n)}[part]
 
 
 def check_device_args(unit='frequency', part='both', reff='auto', who='loo'):
@@ -194,19 +204,6 @@ def check_device_args(unit='frequency', part='both', reff='auto', who='loo'):
     return pair, 0 if reff is None else 1
 
 
-def check_loo_kw(loo_kw, part='both'):
-    """`fit_many(loo_kw=...)` -> dict(unit, reff), checked without a GPU.  A fit of one part has points for units, as `loo` of
-    such a fit has."""
-    kw = dict(loo_kw or {})
-    unknown = sorted(set(kw) - set(LOO_KW))
-    if unknown:
-        raise ValueError('loo_kw: unknown keys %s (known: %s)' % (unknown, list(LOO_KW)))
-    unit, reff = kw.get('unit', 'frequency'), kw.get('reff', 'auto')
-    _pair(unit)
-    check_device_args('point' if part != 'both' else unit, part, reff)
-    return dict(unit='point' if part != 'both' else unit, reff=reff)
-
-
 def chunk_or_default(chunk_bytes):
     """`chunk_bytes` of the device path: None -> 0, the library's default (1 GiB of device scratch per chunk)."""
     if chunk_bytes is None:
@@ -216,22 +213,74 @@ def chunk_or_default(chunk_bytes):
     return int(chunk_bytes)
 
 
-def _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, who, limit):
-    """Checks and the common leading arguments of the two entry points; `r` keeps the reff array alive for the call."""
-    pair, mode = check_device_args(unit, part, reff, who)
+def loo_request(loo, who, need_chains, keys=LOO_KEYS):
+    """The `loo=` request of `engine.sample_units` (need_chains) and `parallel.sample_sharded` (the chains are an argument of
+    its own there), checked without a GPU -> a dict with EVERY key of LOO_KEYS, defaults filled in and 'chains' None where it
+    is not needed: behind this nobody reads a key with a default.  keys: what the caller's request may carry."""
+    kw = dict(loo or {})
+    keys = [k for k in keys if need_chains or k != 'chains']
+    unknown = sorted(set(kw) - set(keys))
+    if unknown:
+        raise ValueError('%s: unknown keys %s (%s %s)' % (who, unknown, 'loo needs chains and takes' if need_chains else 'known:', keys))
+    if need_chains and 'chains' not in kw:
+        raise ValueError('%s: loo needs chains (got %s)' % (who, sorted(kw)))
+    req = dict(LOO_DEFAULTS, **kw)
+    check_device_args(req['unit'], req['part'], req['reff'], who)
+    chunk_or_default(req['chunk_bytes'])
+    return req
+
+
+def check_loo_kw(loo_kw, part='both'):
+    """`fit_many(loo_kw=...)` -> dict(unit, reff), checked without a GPU.  A fit of one part has points for units, as `loo` of
+    such a fit has."""
+    req = loo_request(loo_kw, 'loo_kw', False, LOO_KW)
+    unit = effective_unit(req['unit'], part)
+    check_device_args(unit, part, req['reff'])
+    return dict(unit=unit, reff=req['reff'])
+
+
+def heldout_request(heldout, problem, who):
+    """The `heldout=` request of `engine.sample_units`, checked against the problem without a GPU -> a dict with every key of
+    HELDOUT_KEYS, defaults filled in."""
+    kw = dict(heldout)
+    if set(kw) - set(HELDOUT_KEYS) or not set(HELDOUT_NEEDS) <= set(kw):
+        raise ValueError('%s: heldout needs %s and takes %s (got %s)' % (who, ', '.join(HELDOUT_NEEDS), ', '.join(HELDOUT_DEFAULTS), sorted(kw)))
+    req = dict(HELDOUT_DEFAULTS, **kw)
+    freq, _ = _heldout_grid(problem, req['freq_test'], req['A_test_blocks'], 'heldout', req['sigma_out'])
+    _heldout_part(req['unit'], req['part'], len(freq), 'heldout')
+    chunk_or_default(req['chunk_bytes'])
+    return req
+
+
+def _unit_groups(sampler, unit_lo, unit_hi, chains, who):
+    """Units [unit_lo, unit_hi) of a sampler in groups of `chains` consecutive units -> (unit_lo, unit_hi, chains, G), ints."""
     chains, unit_lo, unit_hi = int(chains), int(unit_lo), int(unit_hi)
     if chains < 1 or unit_lo < 0 or unit_hi > sampler.n_units or unit_hi <= unit_lo or (unit_hi - unit_lo) % chains:
         raise ValueError('%s: units [%d, %d) do not split into groups of %d chains' % (who, unit_lo, unit_hi, chains))
-    if sampler.n_draws < 1:
-        raise ValueError('%s: the sampler holds no draws' % who)
-    S = chains * sampler.n_draws
-    if S > limit:
-        raise ValueError('%s: %d draws per observation, the kernel holds at most %d' % (who, S, limit))
+    return unit_lo, unit_hi, chains, (unit_hi - unit_lo) // chains
+
+
+def _draw_count(S, who, limit, per='unit'):
+    """2 <= S <= limit(): the kernel's limit is asked of the library only when it decides."""
     if S < 2:
         raise ValueError('%s: at least 2 draws are needed' % who)
-    nf = sampler.problem.nf
-    col0, ncols = {'both': (0, 2 * nf), 'real': (0, nf), 'imag': (nf, nf)}[part]
-    G, U = (unit_hi - unit_lo) // chains, ncols // 2 if pair else ncols
+    if S > limit():
+        raise ValueError('%s: %d draws per %s, the kernel holds at most %d' % (who, S, per, limit()))
+
+
+def _sampler_draw_count(sampler, chains, who, limit, per='unit'):
+    if sampler.n_draws < 1:
+        raise ValueError('%s: the sampler holds no draws' % who)
+    _draw_count(chains * sampler.n_draws, who, limit, per)
+
+
+def _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, who, limit):
+    """Checks and the common leading arguments of the two entry points; `r` keeps the reff array alive for the call."""
+    pair, mode = check_device_args(unit, part, reff, who)
+    unit_lo, unit_hi, chains, G = _unit_groups(sampler, unit_lo, unit_hi, chains, who)
+    _sampler_draw_count(sampler, chains, who, limit, 'observation')
+    col0, ncols = part_columns(part, sampler.problem.nf)
+    U = ncols // 2 if pair else ncols
     r = None
     if mode == 1:
         r = _lib.f64(np.broadcast_to(np.asarray(reff, dtype=float), (G, U)))
@@ -247,7 +296,7 @@ def sampler_psis_loo(sampler, unit_lo, unit_hi, chains, unit='frequency', part='
     nor Z_hat, sigma_tot or the log-likelihoods leave the device, which evaluates them in chunks of groups whose scratch stays
     within `chunk_bytes` (None: 1 GiB).  Returns `psis_loo`'s dict, each entry [G, units], plus 'reff', what was used.  With
     reff None, a number or an array every entry equals the host path on the downloaded draws bit for bit."""
-    front, r, G, U, _ = _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, 'psis_loo', max_draws())
+    front, r, G, U, _ = _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes, 'psis_loo', max_draws)
     outs = [np.empty((G, U)) for _ in range(4)]
     n_tail, used = np.empty((G, U), dtype=np.int32), np.empty((G, U))
     _lib.check(sampler._lib.bdrt_sampler_loo(*front, *[_lib.ptr(o) for o in outs], _lib.ptr(n_tail), _lib.ptr(used)),
@@ -262,7 +311,7 @@ def sampler_psis_predict(sampler, unit_lo, unit_hi, chains, unit='frequency', pa
     `psis_predict`'s dict -- the six per-scalar entries [G, columns of the part], pareto_k and n_tail [G, units] -- plus
     'reff'."""
     front, r, G, U, ncols = _sampler_front(sampler, unit_lo, unit_hi, chains, unit, part, reff, chunk_bytes,
-                                           'psis_predict', predict_max_draws())
+                                           'psis_predict', predict_max_draws)
     outs = [np.empty((G, ncols)) for _ in PREDICT_FIELDS]
     k, n_tail, used = np.empty((G, U)), np.empty((G, U), dtype=np.int32), np.empty((G, U))
     _lib.check(sampler._lib.bdrt_sampler_loo_predict(*front, *[_lib.ptr(o) for o in outs], _lib.ptr(k), _lib.ptr(n_tail),
@@ -378,13 +427,6 @@ def _heldout_grid(problem, freq_test, A_test_blocks, who, sigma_out=None):
     return freq, np.ascontiguousarray(np.concatenate(parts))
 
 
-def _heldout_draw_count(S, who):
-    if S < 2:
-        raise ValueError('%s: at least 2 draws are needed' % who)
-    if S > max_draws():
-        raise ValueError('%s: %d draws per unit, the kernel holds at most %d' % (who, S, max_draws()))
-
-
 def heldout_transformed(problem, params, freq_test, A_test_blocks, sigma_out=None):
     """Z_hat and sigma_tot [B, 2 H] (real halves, then imaginary halves) of B rows of CONSTRAINED parameters -- params [B, D]
     as `Problem.transformed` returns them -- at the frequencies freq_test [H], which need not be on the problem's grid, on the
@@ -420,6 +462,22 @@ def _mix_table(table, who):
     return y, w, ey2, int(bool(shared))
 
 
+def _heldout_reduce(who, symbol, Zhat, sig, z, unit, *extra):
+    """The body of `heldout_reduce` and `heldout_mix_reduce`: `symbol` takes the arrays, their sizes, `extra`, then the outputs."""
+    pair, Zhat, sig, z, one = _stacked(who, Zhat, sig, z, unit)
+    G, S, N2 = Zhat.shape
+    if G < 1 or N2 < 1:
+        raise ValueError('%s: empty input' % who)
+    _draw_count(S, who, max_draws)
+    lib = _lib.require_gpu()
+    lpd = np.empty((G, N2 // 2 if pair else N2))
+    outs = [np.empty((G, N2)) for _ in HELDOUT_FIELDS]
+    _lib.check(getattr(lib, symbol)(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, *extra, _lib.ptr(lpd),
+                                    *[_lib.ptr(o) for o in outs]), symbol)
+    res = dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
+    return {key: v[0] for key, v in res.items()} if one else res
+
+
 def heldout_mix_reduce(Zhat, sig_base, z, table, unit='frequency'):
     """`heldout_reduce` under an outlier error model, on the GPU (bdrt_heldout_mix_reduce): sig_base is sigma_tot without
     sigma_out (`heldout_transformed(..., sigma_out='prior')`) and table = (y, w, E[y^2], shared) its prior as an integration rule
@@ -427,28 +485,9 @@ def heldout_mix_reduce(Zhat, sig_base, z, table, unit='frequency'):
     the product of its two normals under one sum (shared) or the product of the two sums; lpd is the log of the draws' mean
     density, mean is `heldout_reduce`'s, sd^2 gains E[y^2], pit is the mean of sum_j w_j Phi.  Definitions:
     tests/heldout_mix_numpy.py.  Same shapes and NaN rule as `heldout_reduce`."""
-    who = 'heldout_mix_reduce'
-    pair = _pair(unit)
-    y, w, ey2, shared = _mix_table(table, who)
-    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig_base), _lib.f64(z)
-    one = Zhat.ndim == 2
-    if one:
-        Zhat, sig, z = Zhat[None], sig[None], z[None]
-    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
-        raise ValueError('%s: shapes %s, %s, %s do not fit' % (who, Zhat.shape, sig.shape, z.shape))
-    G, S, N2 = Zhat.shape
-    if pair and N2 % 2:
-        raise ValueError("%s: unit='frequency' needs an even number of columns, not %d" % (who, N2))
-    if G < 1 or N2 < 1:
-        raise ValueError('%s: empty input' % who)
-    _heldout_draw_count(S, who)
-    lib = _lib.require_gpu()
-    lpd = np.empty((G, N2 // 2 if pair else N2))
-    outs = [np.empty((G, N2)) for _ in HELDOUT_FIELDS]
-    _lib.check(lib.bdrt_heldout_mix_reduce(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, shared, _lib.ptr(y), _lib.ptr(w),
-                                           len(y), ey2, _lib.ptr(lpd), *[_lib.ptr(o) for o in outs]), 'bdrt_heldout_mix_reduce')
-    res = dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
-    return {key: v[0] for key, v in res.items()} if one else res
+    y, w, ey2, shared = _mix_table(table, 'heldout_mix_reduce')
+    return _heldout_reduce('heldout_mix_reduce', 'bdrt_heldout_mix_reduce', Zhat, sig_base, z, unit, shared, _lib.ptr(y), _lib.ptr(w),
+                           len(y), ey2)
 
 
 def heldout_reduce(Zhat, sig, z, unit='frequency'):
@@ -456,33 +495,13 @@ def heldout_reduce(Zhat, sig, z, unit='frequency'):
     (or [S, N2] and [N2]: G = 1).  Returns a dict of lpd [G, units] = logsumexp_s(ll_s) - log S and mean, sd, pit [G, N2] of the
     mixture of the draws' normals -- `psis_loo`'s lpd and `psis_predict`'s mean_post, sd_post, pit_post to the bit, without the
     Pareto fit.  A unit with a non-finite log-likelihood gives NaN, that unit only."""
-    pair = _pair(unit)
-    Zhat, sig, z = _lib.f64(Zhat), _lib.f64(sig), _lib.f64(z)
-    one = Zhat.ndim == 2
-    if one:
-        Zhat, sig, z = Zhat[None], sig[None], z[None]
-    if Zhat.ndim != 3 or sig.shape != Zhat.shape or z.shape != (Zhat.shape[0], Zhat.shape[2]):
-        raise ValueError('heldout_reduce: shapes %s, %s, %s do not fit' % (Zhat.shape, sig.shape, z.shape))
-    G, S, N2 = Zhat.shape
-    if pair and N2 % 2:
-        raise ValueError("heldout_reduce: unit='frequency' needs an even number of columns, not %d" % N2)
-    if G < 1 or N2 < 1:
-        raise ValueError('heldout_reduce: empty input')
-    _heldout_draw_count(S, 'heldout_reduce')
-    lib = _lib.require_gpu()
-    lpd = np.empty((G, N2 // 2 if pair else N2))
-    outs = [np.empty((G, N2)) for _ in HELDOUT_FIELDS]
-    _lib.check(lib.bdrt_heldout_reduce(_lib.ptr(Zhat), _lib.ptr(sig), _lib.ptr(z), G, S, N2, pair, _lib.ptr(lpd),
-                                       *[_lib.ptr(o) for o in outs]), 'bdrt_heldout_reduce')
-    res = dict(zip(HELDOUT_FIELDS, outs), lpd=lpd)
-    return {key: v[0] for key, v in res.items()} if one else res
+    return _heldout_reduce('heldout_reduce', 'bdrt_heldout_reduce', Zhat, sig, z, unit)
 
 
 def _heldout_part(unit, part, H, who):
     """(pair, first column, columns) of the part in the 2 H held-out columns; the checks of `check_device_args`."""
     pair, _ = check_device_args(unit, part, None, who)
-    col0, ncols = {'both': (0, 2 * H), 'real': (0, H), 'imag': (H, H)}[part]
-    return pair, col0, ncols
+    return (pair,) + part_columns(part, H)
 
 
 def sampler_heldout(sampler, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit='frequency', part='both',
@@ -498,17 +517,12 @@ def sampler_heldout(sampler, unit_lo, unit_hi, chains, freq_test, A_test_blocks,
     freq, A = _heldout_grid(sampler.problem, freq_test, A_test_blocks, who, sigma_out)
     H = len(freq)
     pair, col0, ncols = _heldout_part(unit, part, H, who)
-    chains, unit_lo, unit_hi = int(chains), int(unit_lo), int(unit_hi)
-    if chains < 1 or unit_lo < 0 or unit_hi > sampler.n_units or unit_hi <= unit_lo or (unit_hi - unit_lo) % chains:
-        raise ValueError('%s: units [%d, %d) do not split into groups of %d chains' % (who, unit_lo, unit_hi, chains))
-    G = (unit_hi - unit_lo) // chains
+    unit_lo, unit_hi, chains, G = _unit_groups(sampler, unit_lo, unit_hi, chains, who)
     z = np.atleast_2d(_lib.f64(z_test))
     if z.shape != (G, 2 * H):
         raise ValueError('%s: z_test must be [%d, %d] (real halves, then imaginary halves), not %s' % (who, G, 2 * H, z.shape))
     chunk = chunk_or_default(chunk_bytes)
-    if sampler.n_draws < 1:
-        raise ValueError('%s: the sampler holds no draws' % who)
-    _heldout_draw_count(chains * sampler.n_draws, who)
+    _sampler_draw_count(sampler, chains, who, max_draws)
     lpd = np.empty((G, ncols // 2 if pair else ncols))
     outs = [np.empty((G, ncols)) for _ in HELDOUT_FIELDS]
     front = (sampler.handle, unit_lo, unit_hi, chains, pair, col0, ncols, chunk, _lib.ptr(freq), H, _lib.ptr(A), _lib.ptr(z))
@@ -532,7 +546,7 @@ def host_heldout(problem, draws, chains, freq_test, A_test_blocks, z_test, unit=
     draws, z = np.asarray(draws, dtype=float), np.atleast_2d(np.asarray(z_test, dtype=float))
     if draws.ndim != 3 or draws.shape[2] != problem.D or z.shape != (draws.shape[0], 2 * H):
         raise ValueError('%s: draws must be [G, S, %d] and z_test [G, %d]' % (who, problem.D, 2 * H))
-    _heldout_draw_count(draws.shape[1], who)
+    _draw_count(draws.shape[1], who, max_draws)
     cols = slice(col0, col0 + ncols)
     tr = [heldout_transformed(problem, problem.transformed(d)[0], freq, A_test_blocks, sigma_out) for d in draws]
     arrays = (np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
@@ -548,8 +562,8 @@ def _host_arrays(problem, draws, z, part):
     draws, z = np.asarray(draws, dtype=float), np.atleast_2d(np.asarray(z, dtype=float))
     if draws.ndim != 3 or z.shape[0] != draws.shape[0]:
         raise ValueError('draws must be [G, S, D] and z [G, 2 Nf]')
-    nf = z.shape[1] // 2
-    cols = {'both': slice(0, 2 * nf), 'real': slice(0, nf), 'imag': slice(nf, 2 * nf)}[part]
+    col0, ncols = part_columns(part, z.shape[1] // 2)
+    cols = slice(col0, col0 + ncols)
     tr = [problem.transformed(d)[1:] for d in draws]
     return (np.ascontiguousarray(np.stack([t[0] for t in tr])[:, :, cols]),
             np.ascontiguousarray(np.stack([t[1] for t in tr])[:, :, cols]), np.ascontiguousarray(z[:, cols]))

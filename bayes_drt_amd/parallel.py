@@ -283,17 +283,15 @@ _LOO_FIELDS = ('lpd', 'elpd_loo', 'pareto_k', 'p_waic', 'n_tail', 'reff')
 
 
 def _loo_jobs(loo_kw):
-    """[(result key, predict)] of the reductions `loo=` asks for."""
+    """[(result key, predict)] of the reductions the request (`loo.loo_request`'s dict, or None) asks for."""
     if loo_kw is None:
         return []
-    return [(k, p) for k, p, on in (('loo', False, loo_kw.get('loo', True)), ('loo_predict', True, loo_kw.get('predict', False)))
-            if on]
+    return [(k, p) for k, p, on in (('loo', False, loo_kw['loo']), ('loo_predict', True, loo_kw['predict'])) if on]
 
 
 def _loo_call_kw(loo_kw, s_lo, s_hi):
     """Keyword arguments of `Sampler.loo` for spectra [s_lo, s_hi): an array reff [n_spectra, units] is cut to their rows."""
-    kw = dict(unit=loo_kw.get('unit', 'frequency'), part=loo_kw.get('part', 'both'), reff=loo_kw.get('reff', 'auto'),
-              chunk_bytes=loo_kw.get('chunk_bytes'))
+    kw = {k: loo_kw[k] for k in ('unit', 'part', 'reff', 'chunk_bytes')}
     r = kw['reff']
     if r is not None and not isinstance(r, str) and np.ndim(r) == 2:
         kw['reff'] = np.asarray(r, dtype=float)[s_lo:s_hi]
@@ -346,7 +344,6 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
     `loo.relative_efficiency` in the second, which may differ in the last bits of 'reff' ('reff' says what was used)."""
     if gather not in ('draws', 'summary'):
         raise ValueError("gather must be 'draws' or 'summary'")
-    loo_kw = None if loo is None else dict(loo)
     dist = _dist()
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     spec, chain = make_units(n_spectra, chains)
@@ -381,17 +378,13 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
                 if init_theta.shape[1] != D0:
                     raise ValueError('sample_sharded: init_theta has %d columns, the model has D = %d parameters'
                                      % (init_theta.shape[1], D0))
-            if loo_kw is not None:
+            if loo is not None:
                 from . import loo as _loo
-                unknown = sorted(set(loo_kw) - {'loo', 'predict', 'unit', 'part', 'reff', 'chunk_bytes'})
-                if unknown:
-                    raise ValueError('sample_sharded: unknown loo keys %s' % unknown)
-                pair, mode = _loo.check_device_args(loo_kw.get('unit', 'frequency'), loo_kw.get('part', 'both'),
-                                                    loo_kw.get('reff', 'auto'), 'sample_sharded')
-                _loo.chunk_or_default(loo_kw.get('chunk_bytes'))
+                req = _loo.loo_request(loo, 'sample_sharded', need_chains=False)
+                pair, mode = _loo.check_device_args(req['unit'], req['part'], req['reff'], 'sample_sharded')
                 if mode == 1:
-                    ncols = Zfull.shape[1] if loo_kw.get('part', 'both') == 'both' else Zfull.shape[1] // 2
-                    np.broadcast_to(np.asarray(loo_kw['reff'], dtype=float), (n_spectra, ncols // 2 if pair else ncols))
+                    ncols = _loo.part_columns(req['part'], Zfull.shape[1] // 2)[1]
+                    np.broadcast_to(np.asarray(req['reff'], dtype=float), (n_spectra, ncols // 2 if pair else ncols))
                 if chains * n_draws > _loo.max_draws() or chains * n_draws < 2:
                     raise ValueError('sample_sharded: loo needs 2 ... %d draws per spectrum, not %d' % (_loo.max_draws(), chains * n_draws))
             if whole:
@@ -403,6 +396,8 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
     dist.broadcast_object_list(status, src=0, group=group)
     if status[0] is not None:
         raise ValueError('sample_sharded (rank 0): ' + status[0])
+    from .loo import loo_request                                   # (rank 0 has passed the request: every rank normalises it)
+    loo_kw = None if loo is None else loo_request(loo, 'sample_sharded', need_chains=False)
     flat = broadcast_arrays(flat0 if rank == 0 else None, src=0, group=group)
     init_width = int(flat.pop('init_width'))
     init_local = scatter_rows(init_theta, counts, init_width, src=0, group=group) if init_width else None
@@ -436,8 +431,7 @@ def sample_sharded(problem_kwargs, n_spectra, chains, warmup, n_draws, seed=1234
             empty.update(n_eff=np.zeros((0, 0)), Rhat=np.zeros((0, 0)))
         if rank_diagnostics:
             empty['rank'] = {}
-        if loo_kw is not None:
-            empty.update({k: {} for k, on in (('loo', loo_kw.get('loo', True)), ('loo_predict', loo_kw.get('predict', False))) if on})
+        empty.update({k: {} for k, _ in _loo_jobs(loo_kw)})
         return empty
     dd = [(D, np.asarray(worker.is_pos(), dtype=bool).tolist()) if worker is not None else None]
     dist.broadcast_object_list(dd, src=owners[0], group=group)

@@ -198,13 +198,18 @@ def test_sample_units_appends_the_heldout_reduction():
     prob._lib.bdrt_nuts_defaults(C.byref(ctrl))
     ctrl.max_treedepth = 5
     spec, chain = par.make_units(N_SPECTRA, chains)
-    res = sample_units(prob, N_SPECTRA * chains, 30, n_draws, 21, ctrl, spec=spec, chain_ids=chain, loo=dict(chains=chains, reff=None),
+    res = sample_units(prob, N_SPECTRA * chains, 30, n_draws, 21, ctrl, spec=spec, chain_ids=chain, diagnostics_chains=chains,
+                       loo=dict(chains=chains, reff=None),
                        heldout=dict(chains=chains, freq_test=f, A_test_blocks=A, z_test=zt, unit='point'))
-    assert len(res) == 5 and set(res[3]) == {'loo'} and set(res[4]) == set(FIELDS)
+    assert len(res) == 3 and set(res.loo) == {'loo'} and set(res.heldout) == set(FIELDS)
     assert np.array_equal(res[0], smp.results()[0])
     ref = smp.heldout(0, smp.n_units, chains, f, A, zt, unit='point')
     for k in FIELDS:
-        assert np.array_equal(res[4][k], ref[k]), k
+        assert np.array_equal(res.heldout[k], ref[k]), k
+    want = smp.diagnostics(0, smp.n_units, chains)                           # all three extras of one call, each by its name
+    assert len(res.diagnostics) == len(want) == 4
+    for got, exp in zip(res.diagnostics, want):
+        assert np.array_equal(got, exp, equal_nan=True)
 
 
 # ---------------------------------------------------------------------------------------------------- 5: refusals on the device

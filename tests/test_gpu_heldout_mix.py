@@ -253,10 +253,11 @@ def test_sample_units_takes_the_keyword():
     ctrl.max_treedepth = 5
     res = sample_units(prob, 4, 30, 40, 21, ctrl, spec=[0, 0, 0, 0], chain_ids=[0, 1, 2, 3],
                        heldout=dict(chains=2, freq_test=f, A_test_blocks=A, z_test=zt, sigma_out='prior'))
-    assert len(res) == 4 and set(res[3]) == set(FIELDS) and np.array_equal(res[0], smp.results()[0])
+    assert len(res) == 3 and set(res.heldout) == set(FIELDS) and np.array_equal(res[0], smp.results()[0])
+    assert res.diagnostics is None and res.loo is None
     ref = smp.heldout(0, 4, 2, f, A, zt, sigma_out='prior')
     for k in FIELDS:
-        assert np.array_equal(res[3][k], ref[k]), k
+        assert np.array_equal(res.heldout[k], ref[k]), k
 
 
 # ---------------------------------------------------------------------------------------------------- refusals on the device

@@ -216,12 +216,13 @@ def test_sample_units_appends_the_reductions():
     spec, chain = par.make_units(N_SPECTRA, chains)
     res = sample_units(prob, N_SPECTRA * chains, 30, n_draws, 21, ctrl, spec=spec, chain_ids=chain, diagnostics_chains=chains,
                        loo=dict(chains=chains, predict=True, unit='point', reff=0.5))
-    assert len(res) == 5 and set(res[4]) == {'loo', 'predict'}
+    assert len(res) == 3 and set(res.loo) == {'loo', 'predict'} and len(res.diagnostics) == 4 and res.heldout is None
     assert np.array_equal(res[0], smp.results()[0])
-    _assert_equal(res[4]['loo'], smp.loo(0, smp.n_units, chains, unit='point', reff=0.5), LOO_FIELDS + ('reff',), 'loo')
+    _assert_equal(res.loo['loo'], smp.loo(0, smp.n_units, chains, unit='point', reff=0.5), LOO_FIELDS + ('reff',), 'loo')
     ref = smp.loo_predict(0, smp.n_units, chains, unit='point', reff=0.5)
-    _assert_equal(res[4]['predict'], ref, tuple(ref), 'predict')
-    assert len(sample_units(prob, 2, 5, 5, 1, ctrl, spec=[0, 0])) == 3
+    _assert_equal(res.loo['predict'], ref, tuple(ref), 'predict')
+    bare = sample_units(prob, 2, 5, 5, 1, ctrl, spec=[0, 0])
+    assert len(bare) == 3 and bare.diagnostics is None and bare.loo is None and bare.heldout is None
 
 
 # ---------------------------------------------------------------------------------------------------- Inverter surface

@@ -290,6 +290,69 @@ def test_device_entry_points_refuse_before_the_library_loads(no_library):
         sample_units(prob, 6, 5, 5, 1, heldout=dict(chains=2, freq_test=f, A_test_blocks=A, z_test=zt, part='imag'))
 
 
+def test_heldout_request_is_complete_and_checked(no_library):
+    from bayes_drt_amd import loo
+    prob, H = _FakeProblem(), 3
+    f, zt = np.array([10.0, 1.0, 0.1]), np.zeros((3, 2 * H))
+    A = [np.zeros((2 * H, 5)), (np.zeros((H, 4)), np.zeros((H, 4)))]
+    need = dict(chains=2, freq_test=f, A_test_blocks=A, z_test=zt)
+    got = loo.heldout_request(need, prob, 'f')
+    assert set(got) == set(loo.HELDOUT_KEYS) and all(got[k] is v for k, v in need.items())
+    assert (got['unit'], got['part'], got['chunk_bytes'], got['sigma_out']) == ('frequency', 'both', None, None)
+    given = dict(need, unit='point', part='imag', chunk_bytes=1 << 20)
+    assert loo.heldout_request(given, prob, 'f') == dict(given, sigma_out=None)
+    for k in need:
+        with pytest.raises(ValueError, match='f: heldout needs chains, freq_test, A_test_blocks, z_test'):
+            loo.heldout_request({j: v for j, v in need.items() if j != k}, prob, 'f')
+    for kw, msg in ((dict(reff=1), 'heldout needs chains'), (dict(part='imag'), "needs part='both'"), (dict(unit='scalar'), 'unit must be'),
+                    (dict(chunk_bytes=-1), 'chunk_bytes'), (dict(A_test_blocks=A[:1]), 'blocks of prediction rows'),
+                    (dict(sigma_out='posterior'), 'sigma_out must be None'), (dict(sigma_out='prior'), 'needs an outlier error model')):
+        with pytest.raises(ValueError, match=msg):
+            loo.heldout_request(dict(need, **kw), prob, 'f')
+    with pytest.raises(NotImplementedError, match='outlier error models'):
+        loo.heldout_request(need, _FakeProblem(outlier_mode=1), 'f')
+
+
+def test_fit_many_builds_every_held_request_before_the_first_batch(monkeypatch, no_library):
+    """What only `_batch_jobs` can tell -- grids that differ in their last bits and share a batch, outliers='auto' that chose the
+    outlier model -- is refused with no batch started, although an earlier batch was in order."""
+    import copy
+    from bayes_drt_amd.inversion import Inverter
+    f = np.logspace(4, 0, 21)
+    Z = 1.0 + 1.0 / (1.0 + 1j * 2 * np.pi * f * 1e-3)
+    held = (f[:2], Z[:2])
+    inv, started, jobs = Inverter(), [], []
+
+    def fake_jobs(self, frequencies, Z_list, *a, **k):
+        views = [copy.copy(self) for _ in Z_list]
+        for v in views:
+            v._Z_scale = 2.0
+        return views, jobs
+    monkeypatch.setattr(Inverter, '_batch_jobs', fake_jobs)
+    monkeypatch.setattr(Inverter, '_fit_batch', staticmethod(lambda *a, **k: started.append(a)))
+    monkeypatch.setattr(Inverter, '_fit_finish', lambda *a, **k: None)
+    monkeypatch.setattr(Inverter, '_get_prediction_matrices',
+                        lambda self, fr, names: {n: dict(A_re=np.zeros((len(fr), 4)), A_im=np.zeros((len(fr), 4))) for n in names})
+    plain = dict(model_type='Series', outliers=False, sigma_min=0.002)
+    jobs[:] = [dict(plain, batch_key='a'), dict(plain, batch_key='b'), dict(plain, batch_key='b')]
+    grids = [f[2:], f[2:], np.nextafter(f[2:], np.inf)]                      # (the last two: one batch, told apart only by the bits)
+    with pytest.raises(ValueError, match='must share f_test'):
+        inv.fit_many(grids, [Z[2:]] * 3, mode='sample', heldout=[held, held, (f[:2][::-1], Z[:2][::-1])])
+    assert started == []
+    jobs[:] = [dict(plain, batch_key='a'), dict(plain, batch_key='b', outliers=True)]
+    with pytest.raises(NotImplementedError, match='outlier error models'):
+        inv.fit_many(f[2:], [Z[2:]] * 2, mode='sample', outliers='auto', heldout=held)
+    assert started == []
+    # in order: every batch starts with its finished request
+    jobs[:] = [dict(plain, batch_key='a'), dict(plain, batch_key='b'), dict(plain, batch_key='a')]
+    assert len(inv.fit_many(f[2:], [Z[2:]] * 3, mode='sample', heldout=held, heldout_unit='point')) == 3
+    assert [a[11] for a in started] == [[0, 2], [1]]                         # (index)
+    for a in started:
+        h = a[13]
+        assert set(h) == {'chains', 'freq_test', 'A_test_blocks', 'z_test', 'unit', 'part', 'sigma_out'} and h['sigma_out'] is None
+        assert h['unit'] == 'point' and h['z_test'].shape == (len(a[11]), 4) and np.array_equal(h['z_test'][0], np.r_[Z[:2].real, Z[:2].imag] / 2.0)
+
+
 def test_draw_limit_is_refused_on_the_host():
     from bayes_drt_amd import loo
     S = loo.max_draws() + 1

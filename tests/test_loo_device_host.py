@@ -90,6 +90,50 @@ def test_sample_units_checks_its_loo_dict_before_a_sampler_exists():
         sample_units(None, 4, 10, 10, 1, loo=dict(chains=2, unit='both'))
 
 
+def test_sample_result_is_a_triple_with_named_extras():
+    from bayes_drt_amd.engine import SampleResult
+    d, l, g = np.zeros((2, 3, 4)), np.zeros((2, 3)), [{}, {}]
+    res = SampleResult(d, l, g)
+    a, b, c = res
+    assert a is d and b is l and c is g and len(res) == 3 and isinstance(res, tuple) and res[2] is g
+    assert res.diagnostics is None and res.loo is None and res.heldout is None
+    stats, loo, held = (1, 2, 3, 4), {'loo': {}}, {'lpd': 0}
+    res = SampleResult(d, l, g, diagnostics=stats, loo=loo, heldout=held)
+    assert len(res) == 3 and res.diagnostics is stats and res.loo is loo and res.heldout is held
+
+
+def test_loo_request_is_complete_and_checked_once():
+    full = dict(chains=None, loo=True, predict=False, unit='frequency', part='both', reff='auto', chunk_bytes=None)
+    assert tuple(full) == L.LOO_KEYS
+    assert L.loo_request({}, 'f', need_chains=False) == full and L.loo_request(None, 'f', need_chains=False) == full
+    assert L.loo_request(dict(chains=2), 'f', need_chains=True) == dict(full, chains=2)
+    given = dict(chains=4, loo=False, predict=True, unit='point', part='imag', reff=0.5, chunk_bytes=1 << 20)
+    assert L.loo_request(given, 'f', need_chains=True) == given
+    # the request itself is taken as it stands; `check_loo_kw` is where a fit of one part gets points for units
+    assert L.loo_request(dict(unit='point', part='real'), 'f', False)['unit'] == 'point'
+    with pytest.raises(ValueError, match="unit='frequency' needs part='both'"):
+        L.loo_request(dict(part='real'), 'f', False)
+    assert L.check_loo_kw(None, 'real') == dict(unit='point', reff='auto')
+    assert L.check_loo_kw(dict(unit='frequency', reff=None), 'imag') == dict(unit='point', reff=None)
+    assert L.check_loo_kw(dict(unit='frequency'), 'both') == dict(unit='frequency', reff='auto')
+    for kw, need, msg in ((dict(reff=None), True, 'loo needs chains'), (dict(chains=2, parts='real'), True, 'loo needs chains'),
+                          (dict(chains=2, parts='real'), True, r"unknown keys \['parts'\]"),
+                          (dict(chains=2), False, r"unknown keys \['chains'\]"), (dict(unit='pair'), False, "unit must be 'frequency' or 'point', not 'pair'"),
+                          (dict(part='half'), False, "part must be 'both', 'real' or 'imag'"),
+                          (dict(reff='automatic'), False, "reff must be 'auto', None, a number or an array"),
+                          (dict(reff=-1.0), False, 'f: reff must be positive and finite'), (dict(chunk_bytes=-1), False, 'chunk_bytes must not be negative')):
+        with pytest.raises(ValueError, match=msg):
+            L.loo_request(kw, 'f', need)
+    with pytest.raises(ValueError, match=r"loo_kw: unknown keys \['chunk', 'part'\]"):
+        L.check_loo_kw(dict(part='real', chunk=3))
+
+
+def test_the_rules_of_parts_and_units():
+    assert [L.part_columns(p, 3) for p in L.PARTS] == [(0, 6), (0, 3), (3, 3)]
+    assert [L.effective_unit(u, p) for u in L.UNITS for p in ('both', 'real')] == ['frequency', 'point', 'point', 'point']
+    assert L.effective_unit('frequency', 'imag') == 'point'
+
+
 def _header_args(name):
     txt = open(os.path.join(ROOT, 'include', 'bdrt.h')).read()
     txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)

@@ -61,7 +61,7 @@ def time_main(runs):
             t2 = time.perf_counter()
             if reduce:
                 jobs = [dict(outliers=False, model_type=views[0].stan_model_name.split('_')[0])] * n
-                held = Inverter._heldout_job(views, jobs, dict(pairs=[(f[test], Z[test]) for Z in zs], unit='frequency'), 'both', chains)
+                held = Inverter._heldout_job(views, jobs, dict(pairs=[(f[test], Z[test]) for Z in zs], unit='frequency', sigma_out=None), 'both', chains)
                 prob = views[0]._sample_result._model.problem
                 res = loo.host_heldout(prob, np.stack([v._sample_result.theta for v in views]), chains, held['freq_test'],
                                        held['A_test_blocks'], held['z_test'])
