@@ -102,6 +102,8 @@ SYMBOLS = [
     'bdrt_debug_newton_solve', 'bdrt_debug_newton_accept', 'bdrt_debug_qp_factor_solve',
     'bdrt_heldout_transformed', 'bdrt_heldout_reduce', 'bdrt_sampler_heldout',
     'bdrt_heldout_mix_max_nodes', 'bdrt_heldout_mix_transformed', 'bdrt_heldout_mix_reduce', 'bdrt_sampler_heldout_mix',
+    'bdrt_powerscale', 'bdrt_powerscale_max_draws', 'bdrt_sampler_powerscale',
+    'bdrt_debug_powerscale_cjs', 'bdrt_debug_powerscale_weights',
 ]
 
 
@@ -242,6 +244,14 @@ def load_library():
     lib.bdrt_heldout_mix_reduce.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + mix_table + [vp] * 4
     lib.bdrt_sampler_heldout_mix.argtypes = ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp]
                                              + mix_table + [vp] * 4)
+    lib.bdrt_powerscale_max_draws.argtypes = []
+    lib.bdrt_powerscale_max_draws.restype = C.c_int
+    # (problem, theta, spec, G, chains, n_draws, col0, ncols, alpha_lo, alpha_hi, chunk_bytes), then cjs2, pareto_k, n_tail, L_out
+    lib.bdrt_powerscale.argtypes = ([vp, vp, vp] + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_size_t] + [vp] * 4)
+    # (sampler, unit_lo, unit_hi, chains_per_group, col0, ncols, alpha_lo, alpha_hi, chunk_bytes), then cjs2, pareto_k, n_tail
+    lib.bdrt_sampler_powerscale.argtypes = ([vp] + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_size_t] + [vp] * 3)
+    lib.bdrt_debug_powerscale_cjs.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    lib.bdrt_debug_powerscale_weights.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.bdrt_sampler_draws_dev.argtypes = [vp]
     lib.bdrt_sampler_draws_dev.restype = vp
     lib.bdrt_set_device.argtypes = [C.c_int]

@@ -267,6 +267,13 @@ int heldout_of_draws_with(const char *who, const LooDraws &j, const double *freq
 int heldout_mix_of_draws(const LooDraws &j, const double *freq, int H, const double *A, const double *z_test, int shared,
                          const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit);
 
+// Power-scaling sensitivity (bdrt_powerscale.hip) of draws that are on the device, in chunks of groups: j as for loo_of_draws with
+// pair = 0 and reff_mode = 0; every row is evaluated against its group's spectrum.  Outputs on the host: cjs2 [G][D][4] (per
+// constrained parameter: prior lower, prior upper, likelihood lower, likelihood upper), pareto_k, n_tail [G][4], and the two
+// components L_out [G][2][S] (optional); who: the name in error texts
+int powerscale_of_draws(const char *who, const LooDraws &j, double alpha_lo, double alpha_hi, double *cjs2, double *pareto_k,
+                        int *n_tail, double *L_out);
+
 // rank-normalised diagnostics (bdrt_rank.hip) of the same layout of DEVICE draws, on the split chains; outputs [G x C] on the host
 int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride, const unsigned char *is_pos, int G, int M,
                              int N, int C, double p_lo, double p_hi, double *rhat, double *ess_bulk, double *ess_tail,

@@ -861,6 +861,26 @@ int bdrt_sampler_heldout_mix(bdrt_sampler *s, int unit_lo, int unit_hi, int chai
     return heldout_mix_of_draws(j, freq_test, H, A_test, z_test, shared, y, w, Q, ey2, lpd, mean, sd, pit);
 }
 
+int bdrt_sampler_powerscale(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int col0, int ncols, double alpha_lo,
+                            double alpha_hi, size_t chunk_bytes, double *cjs2, double *pareto_k, int *n_tail)
+{
+    const char *who = "bdrt_sampler_powerscale";
+    if (!cjs2 || !pareto_k || !n_tail) { set_error("%s: null argument", who); return -1; }
+    if (!(alpha_lo > 0.0) || !(alpha_lo < 1.0) || !(alpha_hi > 1.0) || !std::isfinite(alpha_hi)) {
+        set_error("%s: the powers need 0 < alpha_lo < 1 < alpha_hi", who);
+        return -1;
+    }
+    std::vector<int> spec;
+    LooDraws j;
+    if (int rc = sampler_loo_job(who, s, unit_lo, unit_hi, chains_per_group, 0, col0, ncols, 0, nullptr, chunk_bytes, spec, j)) return rc;
+    const long rows = (long)chains_per_group * s->impl.np.n_draws;
+    if (rows > bdrt_powerscale_max_draws()) {
+        set_error("%s: %ld draws per column, the kernel holds at most %d", who, rows, bdrt_powerscale_max_draws());
+        return -2;
+    }
+    return powerscale_of_draws(who, j, alpha_lo, alpha_hi, cjs2, pareto_k, n_tail, nullptr);
+}
+
 size_t bdrt_sampler_loo_group_bytes(bdrt_sampler *s, int chains_per_group, int pair, int ncols, int reff_mode, int predict)
 {
     if (!s || chains_per_group < 1 || ncols < 1) return 0;

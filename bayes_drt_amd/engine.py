@@ -410,9 +410,9 @@ class StanModel:
         return res
 
     def sampling(self, data, warmup=200, iter=400, chains=2, seed=1234, init='random', control=None,
-                 chain_ids=None, rounds_per_launch=None, loo=None, heldout=None):
-        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan.  loo, heldout: `sample_units`'
-        arguments; what they reduce is the fit's `device_loo` / `device_heldout`."""
+                 chain_ids=None, rounds_per_launch=None, loo=None, heldout=None, powerscale=None):
+        """NUTS with Jacobian (Stan `sampling`): `iter` counts warm-up + draws, like pystan.  loo, heldout, powerscale:
+        `sample_units`' arguments; what they reduce is the fit's `device_loo` / `device_heldout` / `device_powerscale`."""
         P = self._prepare(data)
         n_draws = int(iter) - int(warmup)
         if n_draws < 0:
@@ -425,7 +425,8 @@ class StanModel:
         if not (init is None or (isinstance(init, str) and init == 'random')):
             init_theta = self._init_theta(init, chains, seed)
         res = sample_units(P, chains, warmup, n_draws, seed, ctrl, init_theta=init_theta,
-                           chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo, heldout=heldout)
+                           chain_ids=chain_ids, rounds_per_launch=rounds_per_launch, loo=loo, heldout=heldout,
+                           powerscale=powerscale)
         draws, lp, diag = res
         theta = draws.reshape(chains * n_draws, P.D)
         fit = StanFit(self, theta, lp.reshape(-1), diag, chains, n_draws,
@@ -434,6 +435,8 @@ class StanModel:
             fit.device_loo = res.loo
         if heldout is not None:
             fit.device_heldout = res.heldout
+        if powerscale is not None:
+            fit.device_powerscale = res.powerscale
         return fit
 
 
@@ -570,6 +573,13 @@ class Sampler:
         from .loo import sampler_heldout
         return sampler_heldout(self, unit_lo, unit_hi, chains, freq_test, A_test_blocks, z_test, unit, part, chunk_bytes, sigma_out)
 
+    def powerscale(self, unit_lo, unit_hi, chains, part='both', lower_alpha=0.99, upper_alpha=1.01, chunk_bytes=None):
+        """Power-scaling prior and likelihood sensitivity of the same groups, reduced where the draws are
+        (bdrt_sampler_powerscale): a dict of cjs2 [groups, D, 4], pareto_k and n_tail [groups, 4].  Arguments:
+        `powerscale.sampler_powerscale`."""
+        from .powerscale import sampler_powerscale
+        return sampler_powerscale(self, unit_lo, unit_hi, chains, part, lower_alpha, upper_alpha, chunk_bytes)
+
     def draws_device(self):
         """The draws where the sampler left them (HBM), as a `__cuda_array_interface__` object."""
         p = self._lib.bdrt_sampler_draws_dev(self.handle)
@@ -589,16 +599,16 @@ class Sampler:
 
 class SampleResult(tuple):
     """What `sample_units` returns: always the tuple (draws, lp, diag); what was reduced while the sampler held the draws is
-    under the attributes `diagnostics`, `loo` and `heldout`, None when not asked for."""
+    under the attributes `diagnostics`, `loo`, `heldout` and `powerscale`, None when not asked for."""
 
-    def __new__(cls, draws, lp, diag, diagnostics=None, loo=None, heldout=None):
+    def __new__(cls, draws, lp, diag, diagnostics=None, loo=None, heldout=None, powerscale=None):
         self = super().__new__(cls, (draws, lp, diag))
-        self.diagnostics, self.loo, self.heldout = diagnostics, loo, heldout
+        self.diagnostics, self.loo, self.heldout, self.powerscale = diagnostics, loo, heldout, powerscale
         return self
 
 
 def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, chain_ids=None, init_theta=None,
-                 rounds_per_launch=None, diagnostics_chains=None, loo=None, heldout=None):
+                 rounds_per_launch=None, diagnostics_chains=None, loo=None, heldout=None, powerscale=None):
     """Run n_units chains (unit u: spectrum spec[u], RNG stream (seed, chain_ids[u])) to completion on the GPU.
     Returns a `SampleResult`: the tuple (draws [n_units, n_draws, D] (unconstrained), lp [n_units, n_draws], list of per-chain
     diagnostics), always of length 3, with the attributes below, each None unless asked for.
@@ -608,8 +618,12 @@ def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, 
     the LOO predictive moments (`Sampler.loo_predict`) of all units while the sampler holds the draws; `.loo` is a dict with the
     entries 'loo' and / or 'predict'.
     heldout=dict(chains=M, freq_test=, A_test_blocks=, z_test=, unit=, part=, chunk_bytes=, sigma_out=): also reduce the predictive of
-    held-out frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; `.heldout` is its dict."""
+    held-out frequencies (`Sampler.heldout`) of all units while the sampler holds the draws; `.heldout` is its dict.
+    powerscale=dict(chains=M, part=, lower_alpha=, upper_alpha=, threshold=, chunk_bytes=): also reduce the power-scaling
+    sensitivity (`Sampler.powerscale`) of all units while the sampler holds the draws; `.powerscale` is its dict."""
     from .loo import heldout_request, loo_request
+    from .powerscale import powerscale_request
+    pkw = None if powerscale is None else powerscale_request(powerscale, 'sample_units', need_chains=True)
     hkw = None if heldout is None else heldout_request(heldout, problem, 'sample_units')
     kw = None if loo is None else loo_request(loo, 'sample_units', need_chains=True)
     with Sampler(problem, n_units, warmup, n_draws, seed, ctrl, spec=spec, chain_ids=chain_ids, init_theta=init_theta) as smp:
@@ -627,6 +641,9 @@ def sample_units(problem, n_units, warmup, n_draws, seed, ctrl=None, spec=None, 
         if hkw is not None:
             res.heldout = smp.heldout(0, n_units, hkw['chains'], hkw['freq_test'], hkw['A_test_blocks'], hkw['z_test'],
                                       hkw['unit'], hkw['part'], hkw['chunk_bytes'], hkw['sigma_out'])
+        if pkw is not None:
+            res.powerscale = smp.powerscale(0, n_units, pkw['chains'], pkw['part'], pkw['lower_alpha'], pkw['upper_alpha'],
+                                            pkw['chunk_bytes'])
         return res
 
 

@@ -975,7 +975,8 @@ class Inverter:
             init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
             mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
             model_str=None, fitY=False, SA=False, SASY=False, n_starts=None, algorithm=None, check_diagnostics=True,
-            loo=False, loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None):
+            loo=False, loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None,
+            powerscale=False, powerscale_kw=None):
         """Fit the distribution(s) with the calibrated hierarchical Bayesian model: mode='optimize' (MAP) or
         'sample' (NUTS).  Arguments as in the reference (:1072-1152), plus two that only concern mode='optimize':
 
@@ -995,9 +996,12 @@ class Inverter:
         loo, loo_predict, loo_kw : mode='sample' only -- as in `fit_many`: `loo_result` / `loo_predict_result` reduced while
             the sampler still holds the draws.
         heldout, heldout_unit, heldout_sigma_out : mode='sample' only -- as in `fit_many`: (f_test, Z_test), frequencies this fit
-            does not see; `heldout_result` is what its draws predict there."""
+            does not see; `heldout_result` is what its draws predict there.
+        powerscale, powerscale_kw : mode='sample' only -- as in `fit_many`: `powerscale_result` reduced while the sampler still
+            holds the draws."""
         self._fit_argument_checks(part, mode, fitY, SA, SASY, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
+        pkw = self._powerscale_arguments(powerscale, powerscale_kw, mode, part)
         hkw = self._heldout_arguments(heldout, heldout_unit, 1, mode, part, [outliers], None, heldout_sigma_out)
         job = self._fit_prepare(frequencies, Z, part, scale_Z, nonneg, outliers, init_from_ridge, ridge_kw, sigma_min,
                                 inductance_scale, outlier_lambda, mode, add_stan_data, model_str, fitY, SA, SASY, n_starts)
@@ -1008,9 +1012,13 @@ class Inverter:
             self._opt_report = model.last_report
         else:
             held = None if hkw is None else self._heldout_job([self], [job], hkw, part, chains)
+            more = {} if pkw is None else dict(powerscale=dict(pkw, chains=chains))
             self._sample_result = model.sampling(dat, warmup=warmup, iter=warmup + samples, chains=chains,
                                                  seed=random_seed, init=job['init'], control=dict(self._NUTS_CONTROL),
-                                                 loo=None if lkw is None else dict(lkw, chains=chains), heldout=held)
+                                                 loo=None if lkw is None else dict(lkw, chains=chains), heldout=held, **more)
+            self._sample_spec = 0
+            if pkw is not None:
+                self._store_device_powerscale(self._sample_result.device_powerscale, 0, pkw, model, chains * samples)
             if lkw is not None:
                 self._store_device_loo(self._sample_result.device_loo, 0, lkw, dat, chains * samples)
             if held is not None:
@@ -1078,7 +1086,8 @@ class Inverter:
                  init_from_ridge=False, ridge_kw={}, sigma_min=0.002, inductance_scale=1, outlier_lambda=None,
                  mode='optimize', random_seed=1234, max_iter=50000, warmup=200, samples=200, chains=2, add_stan_data={},
                  model_str=None, n_starts=None, algorithm=None, group=None, check_diagnostics=True, loo=False,
-                 loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None):
+                 loo_predict=False, loo_kw=None, heldout=None, heldout_unit='frequency', heldout_sigma_out=None,
+                 powerscale=False, powerscale_kw=None):
         """The fits `[copy(self).fit(frequencies, Z, ...) for Z in Z_list]` -- the reference's own workload is such a loop
         over spectra measured on one frequency grid (code_EchemActa/Run fits.ipynb cells 4-5, inversion.py:1072-1081,
         :1218-1221) -- as ONE batch: one shared problem in HBM (the matrices are those of the common grid), every
@@ -1115,9 +1124,15 @@ class Inverter:
         heldout_sigma_out: None, or 'prior': under an outlier error model the held-out point's sigma_out is integrated over its
         prior, which data alone fix (`loo.sigma_out_prior_table`, `loo.heldout_mix_reduce`), and `heldout_result` carries
         sigma_out='prior'; ValueError with outliers=False; with outliers='auto' a spectrum that ends without the outlier model
-        is reduced as without the keyword."""
+        is reduced as without the keyword.
+        powerscale (mode='sample'; ValueError with mode='optimize'): every view also gets `powerscale_result`, what
+        `powerscale_many(views, part=part, **powerscale_kw)` would store -- the power-scaling prior and likelihood sensitivity of
+        every parameter (bayes_drt_amd.powerscale) --, reduced while the sampler still holds the draws (`Sampler.powerscale`), with
+        the same bits.  powerscale_kw: dict with `lower_alpha`, `upper_alpha`, `threshold` (defaults 0.99, 1.01, 0.05); the part
+        is the fit's.  NotImplementedError inside a process group with more than one rank."""
         self._fit_argument_checks(part, mode, False, False, False, n_starts, algorithm)
         lkw = self._loo_arguments(loo, loo_predict, loo_kw, mode, part)
+        pkw = self._powerscale_arguments(powerscale, powerscale_kw, mode, part)
         hkw = self._heldout_arguments(heldout, heldout_unit, len(Z_list), mode, part,
                                       self._per_spectrum(outliers, len(Z_list), 'outliers'), group, heldout_sigma_out)
         if hkw is not None:
@@ -1137,7 +1152,8 @@ class Inverter:
         held = [None if hkw is None else self._heldout_job(v, j, dict(hkw, pairs=[hkw['pairs'][i] for i in idx]), part, chains)
                 for v, j, idx in batches]
         for (v, j, idx), h in zip(batches, held):
-            self._fit_batch(v, j, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics, idx, lkw, h)
+            self._fit_batch(v, j, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics, idx, lkw, h,
+                            pkw)
         for inv, job in zip(views, jobs):
             inv._fit_finish(job, mode, job['sigma_min'], check_outliers)
         return views
@@ -1153,6 +1169,26 @@ class Inverter:
             raise ValueError("loo / loo_predict need the draws of mode='sample'; LOO of a MAP fit is not defined here")
         from . import loo as _loo
         return dict(_loo.check_loo_kw(loo_kw, part), loo=bool(loo), predict=bool(loo_predict), part=part)
+
+    @staticmethod
+    def _powerscale_arguments(powerscale, powerscale_kw, mode, part):
+        """The `powerscale=` dict for the engine (None: not asked for), checked before any GPU work."""
+        if not powerscale:
+            if powerscale_kw is not None:
+                raise ValueError('powerscale_kw is given, but powerscale is not set')
+            return None
+        if mode != 'sample':
+            raise ValueError("powerscale needs the draws of mode='sample'; the sensitivity of a MAP fit is not defined here")
+        from . import powerscale as _ps
+        return _ps.check_powerscale_kw(powerscale_kw, part)
+
+    def _store_device_powerscale(self, res, g, pkw, model, S, index=None):
+        """Row g of the device reduction (`Sampler.powerscale`'s dict) -> `powerscale_result`, through the function
+        `powerscale_many` builds it with."""
+        from . import powerscale as _ps
+        self.powerscale_result = _ps._result(res['cjs2'][g], res['pareto_k'][g], res['n_tail'][g],
+                                             _ps.parameter_names(model.problem, model), pkw['lower_alpha'], pkw['upper_alpha'],
+                                             pkw['threshold'], S, '' if index is None else 'fit %d: ' % index, pkw['part'])
 
     def _store_device_loo(self, res, g, lkw, dat, S, index=None, quiet=False):
         """Row g of the device reductions (`Sampler.loo` / `Sampler.loo_predict` dicts under 'loo' / 'predict') -> `loo_result` /
@@ -1380,9 +1416,10 @@ class Inverter:
 
     @staticmethod
     def _fit_batch(views, jobs, mode, random_seed, max_iter, warmup, samples, chains, algorithm, group, check_diagnostics=False,
-                   index=None, lkw=None, held=None):
+                   index=None, lkw=None, held=None, pkw=None):
         """One engine call for the spectra of one model: fills `_opt_result` / `_sample_result` of every view, with `lkw`
-        (`_loo_arguments`) `loo_result` / `loo_predict_result`, and with `held` (`_heldout_job`) `heldout_result`."""
+        (`_loo_arguments`) `loo_result` / `loo_predict_result`, with `held` (`_heldout_job`) `heldout_result`, and with `pkw`
+        (`_powerscale_arguments`) `powerscale_result`."""
         import ctypes as C
         from . import engine, parallel
         from ._lib import NutsControl
@@ -1454,6 +1491,10 @@ class Inverter:
         from . import diagnostics
         flat = diagnostics.flat_parameter_count(jobs[0]['model_str'], dat)
         param_stats = None
+        ps_res = None
+        if world > 1 and pkw is not None:
+            raise NotImplementedError('fit_many(powerscale=True) inside a process group with more than one rank is out of scope: '
+                                      'run `Inverter.powerscale_many` on the views it returns')
         if world > 1:
             blocks, kw, _ = engine.blocks_from_dat(model.model_name, dat)
             pk = dict(kw, blocks=blocks, Z=np.asarray(dat['Z'], dtype=float), freq=np.asarray(dat['freq'], dtype=float))
@@ -1473,16 +1514,21 @@ class Inverter:
             for k, v in control.items():
                 setattr(ctrl, k, v)
             want = chains if (check_diagnostics and flat <= diagnostics.MAX_FLAT) else None
+            more = {} if pkw is None else dict(powerscale=dict(pkw, chains=chains))
             res = engine.sample_units(P, ns * chains, warmup, n_draws, random_seed, ctrl, spec=spec, chain_ids=chain,
                                       init_theta=init_theta, diagnostics_chains=want,
-                                      loo=None if lkw is None else dict(lkw, chains=chains), heldout=held)
+                                      loo=None if lkw is None else dict(lkw, chains=chains), heldout=held, **more)
             draws, lp, diag = res
             param_stats, loo_res, held_res = res.diagnostics, res.loo, res.heldout
+            ps_res = getattr(res, 'powerscale', None)
         ctl = dict(adapt_delta=control['adapt_delta'], max_treedepth=control.get('max_treedepth', 10))
         for i, inv in enumerate(views):
             u0, u1 = i * chains, (i + 1) * chains
             inv._sample_result = engine.StanFit(model, draws[u0:u1].reshape(chains * n_draws, P.D), lp[u0:u1].reshape(-1),
                                                 diag[u0:u1], chains, n_draws, control=ctl, warmup=warmup)
+            inv._sample_spec = i                                   # the spectrum of the model's problem this view was sampled against
+            if pkw is not None:
+                inv._store_device_powerscale(ps_res, i, pkw, model, chains * n_draws, i if index is None else index[i])
             if lkw is not None:
                 # (with several ranks every rank holds the same results and only rank 0 logs)
                 inv._store_device_loo(loo_res, i, lkw, dat, chains * n_draws, i if index is None else index[i],
@@ -2082,6 +2128,40 @@ class Inverter:
             zs = np.sqrt((r['resid_re'] ** 2 + r['resid_im'] ** 2) / 2)
             return np.argwhere(zs > threshold)
 
+    # ================================================================== prior and likelihood sensitivity (bayes_drt_amd.powerscale)
+    def _powerscale_job(self, part):
+        """(fit, scaled data, columns, spectrum index) of this instance's sampling fit for `powerscale`."""
+        if self.fit_type != 'bayes':
+            raise ValueError('Power-scaling sensitivity is only available for bayes_fit')
+        fit, z, columns, _ = self._loo_job(part)
+        return fit, z, columns, int(getattr(self, '_sample_spec', 0))
+
+    def powerscale(self, part='both', lower_alpha=0.99, upper_alpha=1.01, threshold=0.05):
+        """Power-scaling sensitivity of this instance's sampling fit (bayes_drt_amd.powerscale.powerscale; Kallioinen et al. 2023):
+        for every parameter, how far its marginal posterior moves when the prior, and when the likelihood, is raised to a power
+        near 1 -- estimated from the draws by Pareto-smoothed importance sampling, without a refit.  A parameter with prior and
+        likelihood sensitivity at or above `threshold` is in 'prior-data conflict'; with the prior's alone the prior decides it
+        ('strong prior / weak likelihood').  part: 'real' / 'imag' for a fit of that part alone (only that half's observations are
+        the likelihood).  Returns a `PowerscaleResult` -- names, prior, likelihood, diagnosis, cjs2, pareto_k, n_tail, alphas,
+        threshold, n_draws; `.flagged()`, `print(result)` -- and stores it as `powerscale_result`."""
+        from . import powerscale as _ps
+        fit, z, columns, spec = self._powerscale_job(part)
+        self.powerscale_result = _ps.powerscale(fit, z, columns, lower_alpha, upper_alpha, threshold, spec)
+        return self.powerscale_result
+
+    @staticmethod
+    def powerscale_many(inverters, part='both', lower_alpha=0.99, upper_alpha=1.01, threshold=0.05, chunk_bytes=None):
+        """`powerscale()` of every Inverter of a list (what `fit_many` returns): fits that share their problem go through one
+        launch of each kernel per chunk of at most `chunk_bytes` of device scratch (None: 1 GiB).  Returns the results in input
+        order, each bit for bit what the Inverter's own `powerscale()` gives, and stores each as `powerscale_result`."""
+        from . import powerscale as _ps
+        jobs = [inv._powerscale_job(part) for inv in inverters]
+        res = _ps.powerscale_many([j[0] for j in jobs], [j[1] for j in jobs], jobs[0][2] if jobs else None, lower_alpha,
+                                  upper_alpha, threshold, chunk_bytes, [j[3] for j in jobs])
+        for inv, r in zip(inverters, res):
+            inv.powerscale_result = r
+        return res
+
     # ================================================================== K-fold and exact refits (bayes_drt_amd.loo)
     def _pinned_copy(self, frequencies):
         """A copy of this instance whose basis is that of the full grid `frequencies` whatever rows a refit drops: `basis_freq` of
@@ -2444,7 +2524,7 @@ class Inverter:
                        'detail': ['distribution_matrices']},
             'ridge': {'core': [], 'detail': ['_iter_history']},
             'map': {'core': ['stan_model_name', 'error_fit'], 'detail': ['_stan_input', '_init_params', '_opt_result']},
-            'bayes': {'core': ['stan_model_name', '_sample_result', 'error_fit'], 'detail': ['_stan_input', '_init_params']},
+            'bayes': {'core': ['stan_model_name', '_sample_result', 'error_fit'], 'detail': ['_stan_input', '_init_params', 'powerscale_result']},
         }
         if which == 'all':
             return sum(fit_attributes['common'].values(), []) + sum(fit_attributes[self.fit_type].values(), [])

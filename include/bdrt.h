@@ -454,6 +454,29 @@ int bdrt_heldout_mix_reduce(const double *Zhat, const double *sig_base, const do
 int bdrt_sampler_heldout_mix(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int pair, int col0, int ncols,
                              size_t chunk_bytes, const double *freq_test, int H, const double *A_test, const double *z_test, int shared,
                              const double *y, const double *w, int Q, double ey2, double *lpd, double *mean, double *sd, double *pit);
+/* ---- (4d) power-scaling prior and likelihood sensitivity -----
+ * Kallioinen, Paananen, Buerkner, Vehtari 2023; definitions: tests/powerscale_numpy.py.  Per fit of S = chains * n_draws draws:
+ * the components L_lik = the sum of the pointwise log-likelihoods of scalar observations [col0, col0 + ncols) of the 2 Nf and
+ * L_pri = lp0 - L_lik, lp0 the log density without the Jacobian term against the fit's spectrum; four weight vectors, the
+ * Pareto-smoothed normalised importance weights of (alpha - 1) L at reff = 1 in the order (prior, alpha_lo), (prior, alpha_hi),
+ * (likelihood, alpha_lo), (likelihood, alpha_hi); per constrained parameter (the D columns bdrt_transformed writes) and weight
+ * vector cjs2, the squared cumulative Jensen-Shannon distance (base 2, in [0, 1]) between the column's ECDF and the re-weighted
+ * one, the larger of the value on the distribution and on the survival functions; ties are ordered by draw index.
+ * Outputs on the host: cjs2 [G][D][4], pareto_k and n_tail [G][4] (inf and the raw weights when at most 4 ratios lie above the
+ * cutoff or the component is constant).  A component with a non-finite entry gives NaN in its weights, its pareto_k and its
+ * cjs2 (n_tail 0); a column with a non-finite value NaN; a constant column 0.  0 < alpha_lo < 1 < alpha_hi.
+ * 2 <= S <= bdrt_powerscale_max_draws() (8192; -2 above).  Bit-reproducible, and a fit's results do not depend on what else is in
+ * the call or on chunk_bytes (one chunk's device scratch, as in bdrt_sampler_loo; 0: 1 GiB).
+ *
+ * On host draws: theta [G * S][D] unconstrained, chain-major per fit; spec [G] (NULL: 0) the spectrum of each fit.
+ * L_out [G][2][S] (may be NULL): L_pri, L_lik. */
+int bdrt_powerscale_max_draws(void);
+int bdrt_powerscale(bdrt_problem *p, const double *theta, const int *spec, int G, int chains, int n_draws, int col0, int ncols,
+                    double alpha_lo, double alpha_hi, size_t chunk_bytes, double *cjs2, double *pareto_k, int *n_tail, double *L_out);
+/* The same on the draws a sampler holds, groups as in bdrt_sampler_loo: nothing but the result planes crosses the bus.  Every
+ * output equals bdrt_powerscale on the downloaded draws bit for bit. */
+int bdrt_sampler_powerscale(bdrt_sampler *s, int unit_lo, int unit_hi, int chains_per_group, int col0, int ncols, double alpha_lo,
+                            double alpha_hi, size_t chunk_bytes, double *cjs2, double *pareto_k, int *n_tail);
 /* device pointer of the draws [n_units x n_draws x D] (unconstrained), valid until bdrt_sampler_destroy: lets a
  * collective library (RCCL) gather draws without a host round trip.  Synchronises the sampler's stream. */
 const double *bdrt_sampler_draws_dev(bdrt_sampler *s);
@@ -480,6 +503,13 @@ int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H
  * draws themselves as the kernel stages them, i.e. exp(y) when is_pos != 0 (the device's exp, which may differ from the
  * host's in the last bit). */
 int bdrt_debug_rank_z(const double *y, int M, int N, int is_pos, int what, double *z_out);
+/* The two kernels of bdrt_powerscale on supplied data (no problem handle; the current device).
+ * The distance kernel: columns X [C][S] and weight vectors w [4][S], taken as they are -> cjs2 [C][4].
+ * The weights kernel: components L [G][2][S] -> the log weights lw and the weights w [G][4][S] (either may be NULL), pareto_k,
+ * n_tail [G][4].  2 <= S <= bdrt_powerscale_max_draws() (-2 above), C <= 65535. */
+int bdrt_debug_powerscale_cjs(const double *X, const double *w, int C, int S, double *cjs2);
+int bdrt_debug_powerscale_weights(const double *L, int G, int S, double alpha_lo, double alpha_hi, double *lw, double *w,
+                                  double *pareto_k, int *n_tail);
 
 /* One launch of the Newton iteration's damped solve on supplied data (no problem handle; the current device):
  * newton_build_kernel (M = -H + lam I from H), newton_solve_kernel with `natt` attempts (1 .. 6) side by side,
