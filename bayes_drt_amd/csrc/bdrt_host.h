@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -54,6 +55,14 @@ struct LdsAttrCache {
         e = set_attrs();
         if (e == hipSuccess && dev >= 0 && dev < 64) hw[dev] = bytes;
         return e;
+    }
+    // the common case: every kernel of `fns` gets the limit `bytes`
+    hipError_t raise(size_t bytes, std::initializer_list<const void *> fns)
+    {
+        return ensure(bytes, [&]() {
+            hipError_t e = hipSuccess;
+            for (const void *f : fns) if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            return e; });
     }
 };
 
@@ -279,19 +288,9 @@ int rank_diagnostics_to_host(const double *dX, long unit_stride, long row_stride
                              int N, int C, double p_lo, double p_hi, double *rhat, double *ess_bulk, double *ess_tail,
                              double *ess_mean, double *sd, hipStream_t stream);
 
-// Levenberg-Marquardt Newton polish of n_fits points on the device (bdrt_newton.hip); x0 / x_out [n_fits][D] on the host
-int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
-                         double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out);
-
-// closed-form Hessian at one point (bdrt_newton_hess.h; tests): 1 when the problem has none.  lin: the coefficients on the linear
-// scale (Series_pos only, else 1); held_out [D] (optional): the coefficients held at their floor
-int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double *H_out, double *held_out);
-
-// one launch of the damped solve / of the verdict on supplied data (tests; include/bdrt.h, debug section): no problem, the current device
-int newton_solve_at(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz, const double *held,
-                    double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out, bdrt_newton_solve_record *rec);
-int newton_accept_at(bdrt_newton_state *st, double *x, double *g, int D, const double *trial, const double *lp_t, const double *gt,
-                     const double *tz, const double *held, double floor_x, int o_x, int Kx);
+// Levenberg-Marquardt Newton polish of n_fits points on the device (bdrt_newton.hip); x0 / x_out [n_fits][D], rep [n_fits] on the host
+struct NewtonReport { double lp, grad_inf; int iters, rc, n_evals; };
+int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out, NewtonReport *rep);
 
 // the dynamic LDS of the kernels around the box-QP solver (bdrt_qp.hip: bdrt_qp_box_batch, bdrt_ridge_ex, bdrt_debug_qp_factor_solve)
 // for n unknowns and `extra` doubles of the kernel's own: whether the packed KKT triangle lives in LDS (else in a global work

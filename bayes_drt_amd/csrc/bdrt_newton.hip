@@ -15,8 +15,12 @@
 //                                                                            newton_solve_kernel   (one workgroup per fit)
 //   trial       log-posterior + gradient at x + s, x + s/2, x + s/4, x + s/8   launch_logp_grad
 //   decision    accept / reject, lam update, convergence                     newton_accept_kernel
-// The host only sequences these launches and reads the status records; fits of a batch advance together.
+// The host only sequences these launches and reads the status records; fits of a batch advance together.  Its pieces, after the kernels:
+// NewtonEnv (the switches, read once per call), NewtonWork (every device buffer, the NewtonBufs the kernels take, the LDS limits, the host
+// synchronisation), group_length, enqueue_round (the launches of one round) and newton_polish_device, which puts them in order.  The debug
+// entries at the end (bdrt_debug_hessian(_lin), bdrt_debug_newton_solve / _accept) fill a NewtonWork with what their launches touch.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -670,233 +674,308 @@ __global__ __launch_bounds__(256) void newton_init_kernel(NewtonBufs b, int n_fi
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- host side
 // dynamic LDS of newton_solve_kernel: right-hand side, reduction scratch, chol_blocked's diagonal block, pivots, panel and flag
 static size_t newton_solve_lds_bytes(int Dp)
 {
     return ((size_t)Dp + 64 + 16 * 17 + 16 + (size_t)Dp * 17 + 2) * sizeof(double);
 }
 
-// Newton polish of n_fits points (x0 [n_fits][D] on the host); results back to x_out, reports filled
-int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out,
-                         double *lp_out, double *ginf_out, int *iters_out, int *rc_out, int *n_evals_out)
+// The switches of the iteration (measurements: DESIGN 7b), read once per newton_polish_device call; the test entries read none.
+struct NewtonEnv {
+    bool spec = true;           // BDRT_NEWTON_SPEC=0: never more than one factorisation per launch
+    bool fd = false;            // BDRT_NEWTON_FD=1: central differences of the gradient (as in rounds 1-5) where the model has a closed form, too
+    bool linear = true;         // BDRT_NEWTON_LINEAR=0: the coefficients stay on the log scale for the whole iteration
+    bool prof = false;          // BDRT_NEWTON_PROF=1: cycle counters of the kernels' phases and the host's times, on stderr
+    bool trial_few = true;      // BDRT_NEWTON_TRIAL_FEW=0: the trial points through the tile evaluator (as before round 6)
+    bool trace = false;         // BDRT_NEWTON_TRACE=1: the status records of the first eight fits at every host synchronisation, on stderr
+    bool rounds_set = false;    // BDRT_NEWTON_ROUNDS=<n>: n rounds between host synchronisations, and no group twice as long (group_length)
+    int rounds = 4;
+};
+
+static NewtonEnv read_newton_env()
 {
-    const int D = P.dev.D, Dp = (D + 15) & ~15;
-    BDRT_HIP(hipSetDevice(P.device));
-    const auto t_host0 = std::chrono::steady_clock::now();
+    auto is = [](const char *name, char c) { const char *e = getenv(name); return e && e[0] == c; };
+    NewtonEnv e;
+    e.spec = !is("BDRT_NEWTON_SPEC", '0'); e.fd = is("BDRT_NEWTON_FD", '1'); e.linear = !is("BDRT_NEWTON_LINEAR", '0');
+    e.prof = is("BDRT_NEWTON_PROF", '1'); e.trial_few = !is("BDRT_NEWTON_TRIAL_FEW", '0'); e.trace = is("BDRT_NEWTON_TRACE", '1');
+    if (const char *r = getenv("BDRT_NEWTON_ROUNDS")) { e.rounds_set = true; e.rounds = std::max(1, atoi(r)); }
+    return e;
+}
+
+// Every device buffer of the iteration, the NewtonBufs the kernels take, and the host's copies of the status records and lists.  The iteration
+// sizes all of it (alloc); a test entry fills the few owners its launches touch.  bind() is the one place where NewtonBufs gets its pointers: an
+// owner that was not allocated reads as nullptr (M2, pgrad, plp, hws, prof where the iteration does without them).
+struct NewtonWork {
     NewtonBufs b;
-    b.D = D; b.Dp = Dp;
-    const size_t nD = (size_t)n_fits * D, nM = (size_t)n_fits * Dp * Dp;
     DevBuf<double> x, g, s, xt, gt, hstep, H, M, M2, probes, pgrad, plp, hws, lpt;
     DevBuf<NewtonAttempt> att;
-    DevBuf<NewtonState> dst;
+    DevBuf<NewtonState> state;
     DevBuf<long long> prof;
     DevBuf<int> active, spec1, specp, fspec;
-    BDRT_HIP(x.alloc(nD)); BDRT_HIP(g.alloc(nD)); BDRT_HIP(s.alloc(NW_ATT * nD));
-    BDRT_HIP(xt.alloc(NW_ATT * nD)); BDRT_HIP(gt.alloc(nD * NW_TRY)); BDRT_HIP(hstep.alloc(nD));
-    BDRT_HIP(att.alloc((size_t)n_fits * NW_ATT));
-    BDRT_HIP(hipMemsetAsync(att, 0, (size_t)n_fits * NW_ATT * sizeof(NewtonAttempt), P.stream));
-    BDRT_HIP(H.alloc(nM));
-    BDRT_HIP(M.alloc(nM));
-    // the speculative factorisations (newton_solve_kernel) need matrices of their own: allocated while they stay below 2 GB (a 512-spectrum batch with them -- 2.3 GB of hipMalloc -- was 0.31 -> 0.38 s), used in the
-    // launches that have the workgroups to spare (BDRT_NEWTON_SPEC=0: never)
-    int n_cu = 0;
-    BDRT_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P.device));
-    const char *spec_env = getenv("BDRT_NEWTON_SPEC");
-    if (!(spec_env && spec_env[0] == '0') && (NW_ATT - 1) * nM * sizeof(double) <= ((size_t)2 << 30))
-        BDRT_HIP(M2.alloc((NW_ATT - 1) * nM));
-    // closed-form Hessian where the model has one (BDRT_NEWTON_FD=1: central differences of the gradient as in rounds 1-5)
-    const char *fd_env = getenv("BDRT_NEWTON_FD");
-    b.analytic = (hess_analytic_ok(P.dev) && !(fd_env && fd_env[0] == '1')) ? 1 : 0;
-    b.dP = (const DevProblem *)P.d_dev;
-    const HessLayout hlay(P.dev.nf, P.dev.blk[0].K);
-    b.hl_total = hlay.total; b.hl_tz = hlay.tz; b.hl_act = hlay.act; b.hl_floor = hlay.h0 + 11; b.o_x = P.dev.blk[0].o_x; b.Kx = P.dev.blk[0].K;
-    const char *lin_env = getenv("BDRT_NEWTON_LINEAR");      // 0: the coefficients stay on the log scale for the whole iteration
-    b.lin_ok = (b.analytic && P.dev.blk[0].is_pos && !(lin_env && lin_env[0] == '0')) ? 1 : 0;
-    if (b.analytic) {
-        // (the probe buffer only carries the trial points of a round)
-        BDRT_HIP(probes.alloc(nD * NW_TRY));
-        BDRT_HIP(hws.alloc((size_t)n_fits * hlay.total));
-    } else {
-        BDRT_HIP(probes.alloc(2 * nD * D));
-        BDRT_HIP(pgrad.alloc(2 * nD * D));
-        BDRT_HIP(plp.alloc(2 * nD));
+    size_t lds_prep = 0, lds_fill = 0, lds_solve = 0;      // dynamic LDS of hess_prep / accept_prep, hess_fill, solve
+    // the host's side of a synchronisation (sync_active)
+    std::vector<NewtonState> hst;
+    std::vector<int> hspec, hact, hact_prev, hspecp, sp1;
+    int n_active = 0;
+    double g_far = 0.0;         // largest |g| of the active fits
+    explicit NewtonWork(int D) { memset(&b, 0, sizeof(b)); b.D = D; b.Dp = (D + 15) & ~15; lds_solve = newton_solve_lds_bytes(b.Dp); }
+    // the problem whose closed-form Hessian the kernels evaluate (analytic = 0: they difference gradients) and its workspace's layout
+    void model(const Problem &P, int analytic, int lin_ok)
+    {
+        const int nf = P.dev.nf, K = P.dev.blk[0].K;
+        const HessLayout hlay(nf, K);
+        b.dP = (const DevProblem *)P.d_dev; b.analytic = analytic; b.lin_ok = lin_ok;
+        b.hl_total = hlay.total; b.hl_tz = hlay.tz; b.hl_act = hlay.act; b.hl_floor = hlay.h0 + 11; b.o_x = P.dev.blk[0].o_x; b.Kx = K;
+        lds_prep = analytic ? hess_prep_lds_doubles(nf, K) * sizeof(double) : 0;
+        lds_fill = analytic ? hess_fill_lds_doubles(nf, K) * sizeof(double) : 0;
     }
-    BDRT_HIP(dst.alloc((size_t)n_fits));
-    const char *prof_env = getenv("BDRT_NEWTON_PROF");
-    if (prof_env && prof_env[0] == '1') {
-        BDRT_HIP(prof.alloc(NP_COUNT));
-        BDRT_HIP(hipMemset(prof, 0, NP_COUNT * sizeof(long long)));
-        BDRT_HIP(hipStreamSynchronize(nullptr));          // the fill is asynchronous; the kernels run on the problem's own stream
+    // The iteration's buffers for n fits, after model().  The sizing rules: M2, the matrices of the speculative factorisations
+    // (newton_solve_kernel), only with speculation and while they stay below 2 GB (a 512-spectrum batch with them -- 2.3 GB of hipMalloc --
+    // was 0.31 -> 0.38 s); closed form: probes holds only the NW_TRY trial points of a round, and there is the Hessian's workspace hws;
+    // differences: probes holds the 2 D probes of a fit, pgrad and plp their gradients and log-posteriors; prof only when profiling.
+    int alloc(size_t n, const NewtonEnv &env, hipStream_t stream)
+    {
+        const size_t D = b.D, nD = n * D, nM = n * b.Dp * b.Dp;
+        BDRT_HIP(x.alloc(nD)); BDRT_HIP(g.alloc(nD)); BDRT_HIP(s.alloc(NW_ATT * nD));
+        BDRT_HIP(xt.alloc(NW_ATT * nD)); BDRT_HIP(gt.alloc(nD * NW_TRY)); BDRT_HIP(hstep.alloc(nD));
+        BDRT_HIP(att.alloc(n * NW_ATT));
+        BDRT_HIP(hipMemsetAsync(att, 0, n * NW_ATT * sizeof(NewtonAttempt), stream));
+        BDRT_HIP(H.alloc(nM)); BDRT_HIP(M.alloc(nM));
+        if (env.spec && (NW_ATT - 1) * nM * sizeof(double) <= ((size_t)2 << 30)) BDRT_HIP(M2.alloc((NW_ATT - 1) * nM));
+        BDRT_HIP(probes.alloc(b.analytic ? nD * NW_TRY : 2 * nD * D));
+        if (b.analytic) BDRT_HIP(hws.alloc(n * b.hl_total));
+        else { BDRT_HIP(pgrad.alloc(2 * nD * D)); BDRT_HIP(plp.alloc(2 * nD)); }
+        BDRT_HIP(state.alloc(n));
+        if (env.prof) {
+            BDRT_HIP(prof.alloc(NP_COUNT));
+            BDRT_HIP(hipMemset(prof, 0, NP_COUNT * sizeof(long long)));
+            BDRT_HIP(hipStreamSynchronize(nullptr));          // the fill is asynchronous; the kernels run on the problem's own stream
+        }
+        BDRT_HIP(active.alloc(n)); BDRT_HIP(spec1.alloc(n * NW_TRY)); BDRT_HIP(specp.alloc(n * (b.analytic ? 1 : 2 * D)));
+        BDRT_HIP(fspec.alloc(n)); BDRT_HIP(lpt.alloc(n * NW_TRY));
+        bind();
+        return 0;
     }
-    BDRT_HIP(active.alloc((size_t)n_fits));
-    BDRT_HIP(spec1.alloc((size_t)n_fits * NW_TRY));
-    BDRT_HIP(specp.alloc((size_t)n_fits * (b.analytic ? 1 : 2 * D)));
-    BDRT_HIP(fspec.alloc((size_t)n_fits));
-    BDRT_HIP(lpt.alloc((size_t)n_fits * NW_TRY));
-    // (an owner that was not allocated reads as nullptr: M2, pgrad, plp, hws, prof where the iteration does without them)
-    b.x = x; b.g = g; b.s = s; b.xt = xt; b.gt = gt; b.hstep = hstep; b.att = att; b.H = H; b.M = M; b.M2 = M2; b.probes = probes;
-    b.pgrad = pgrad; b.plp = plp; b.hws = hws; b.st = dst; b.prof = prof; b.fspec = fspec;
-    int *const d_active = active, *const d_spec1 = spec1, *const d_specp = specp;
-    double *const d_lpt = lpt;
-    std::vector<NewtonState> hst((size_t)n_fits);
-    for (auto &s : hst) { memset(&s, 0, sizeof(s)); s.lam = 1e-3; s.max_iter = max_iter; s.tol = tol; s.rc = 1; s.done = max_iter > 0 ? 0 : 1; }
-    BDRT_HIP(hipMemcpy(b.st, hst.data(), hst.size() * sizeof(NewtonState), hipMemcpyHostToDevice));
-    BDRT_HIP(hipMemcpy(b.x, x0, nD * sizeof(double), hipMemcpyHostToDevice));
+    // A test entry's one fit: its point, gradient and state up, the active list {0}, and a stand-in for the closed-form Hessian's
+    // workspace: the three fields the solve, gather and accept kernels read -- tz [D], act [D], the floor -- and the layout offsets
+    // that point at them (tz == nullptr: the log scale, no workspace)
+    int one_fit(const double *x_, const double *g_, const NewtonState &hs, const double *tz, const double *held, double floor_x, int o_x, int Kx)
+    {
+        const int D = b.D, zero = 0;
+        if (upload(x, x_, (size_t)D) || upload(g, g_, (size_t)D) || upload(state, &hs, 1) || upload(active, &zero, 1)) return -10;
+        if (!tz) return 0;
+        std::vector<double> w((size_t)2 * D + 1);
+        for (int i = 0; i < D; ++i) { w[i] = tz[i]; w[(size_t)D + i] = held && held[i] != 0.0 ? 1.0 : 0.0; }
+        w[(size_t)2 * D] = floor_x;
+        if (upload(hws, w.data(), w.size())) return -10;
+        b.analytic = 1; b.lin_ok = 1;
+        b.hl_total = 2 * D + 1; b.hl_tz = 0; b.hl_act = D; b.hl_floor = 2 * D; b.o_x = o_x; b.Kx = Kx;
+        return 0;
+    }
+    void bind()
+    {
+        b.x = x; b.g = g; b.gt = gt; b.hstep = hstep; b.s = s; b.xt = xt; b.H = H; b.M = M; b.M2 = M2; b.att = att; b.probes = probes;
+        b.pgrad = pgrad; b.plp = plp; b.st = state; b.prof = prof; b.hws = hws; b.fspec = fspec;
+    }
+    // the kernels that take more dynamic LDS than a launch gets by default: their limits, raised once per device and size
+    int raise_lds_limits() const
+    {
+        static LdsAttrCache prep, fill, solve;
+        BDRT_HIP(prep.raise(lds_prep, {(const void *)newton_hess_prep_kernel, (const void *)newton_accept_prep_kernel}));
+        BDRT_HIP(fill.raise(lds_fill, {(const void *)newton_hess_fill_kernel}));
+        BDRT_HIP(solve.raise(lds_solve, {(const void *)newton_solve_kernel}));
+        return 0;
+    }
+    // (what the profile times as "frees": the matrices and vectors go here and not at the closing brace)
+    void release_arrays() { for (DevBuf<double> *d : {&M2, &H, &M, &s, &xt, &gt, &probes, &pgrad, &hws, &x, &g, &hstep, &plp, &lpt}) d->reset(); }
+    // the start of the iteration: the fits' states and points up (x0 [n][D], spec [n] or null on the host)
+    int start(const double *x0, const int *spec, int n, int max_iter, double tol, hipStream_t stream)
+    {
+        hst.resize((size_t)n); hspec.resize((size_t)n); hact.resize((size_t)n);
+        for (auto &h : hst) { memset(&h, 0, sizeof(h)); h.lam = 1e-3; h.max_iter = max_iter; h.tol = tol; h.rc = 1; h.done = max_iter > 0 ? 0 : 1; }
+        BDRT_HIP(hipMemcpy(b.st, hst.data(), hst.size() * sizeof(NewtonState), hipMemcpyHostToDevice));
+        BDRT_HIP(hipMemcpy(b.x, x0, (size_t)n * b.D * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < n; ++i) hspec[i] = spec ? spec[i] : 0;
+        return (upload(spec1.p, hspec.data(), (size_t)n, stream) || upload(fspec.p, hspec.data(), (size_t)n, stream)) ? -10 : 0;
+    }
+    // One host synchronisation, ~90 us: the status records down, the list of the fits that go on and its spectrum ids (one per trial
+    // point; one per probe when gradients are differenced) up -- the lists only when they changed.
+    int sync_active(hipStream_t stream)
+    {
+        if (download(hst.data(), b.st, hst.size(), stream)) return -10;
+        BDRT_HIP(hipStreamSynchronize(stream));
+        n_active = 0; g_far = 0.0;
+        for (int i = 0; i < (int)hst.size(); ++i) if (!hst[i].done) { hact[n_active++] = i; g_far = std::max(g_far, hst[i].grad_inf); }
+        if (n_active == 0 || ((int)hact_prev.size() == n_active && std::equal(hact_prev.begin(), hact_prev.end(), hact.begin()))) return 0;
+        hact_prev.assign(hact.begin(), hact.begin() + n_active);
+        sp1.clear(); hspecp.clear();
+        for (int f : hact_prev) { sp1.insert(sp1.end(), NW_TRY, hspec[f]); if (!b.analytic) hspecp.insert(hspecp.end(), (size_t)2 * b.D, hspec[f]); }
+        return (upload(active.p, hact.data(), (size_t)n_active, stream) || (!b.analytic && upload(specp.p, hspecp.data(), hspecp.size(), stream)) ||
+                upload(spec1.p, sp1.data(), sp1.size(), stream)) ? -10 : 0;
+    }
+};
+
+// Rounds between two host synchronisations: twice as many while some active fit is far from its stationary point (|g| > 0.01: at least three more
+// rounds) -- small batches only: a fit that finishes inside a group keeps its rows in the evaluator's batch until the next synchronisation
+static int group_length(const NewtonEnv &env, double g_far, int n_active) { return (env.rounds_set || !(g_far > 1e-2) || n_active > 32) ? env.rounds : 2 * env.rounds; }
+
+// One Levenberg-Marquardt round of the active fits, enqueued on the problem's stream.  The sequence of launches does not depend on
+// what the round decides (kernels skip the fits that are done; a fit that keeps its Hessian after a rejected trial skips the probe
+// writes and ignores the probe gradients), so several rounds are enqueued back to back.
+static int enqueue_round(Problem &P, const NewtonWork &w, bool trial_few, int natt, bool first)
+{
+    const NewtonBufs &b = w.b;
+    const int D = b.D, Dp = b.Dp, n_active = w.n_active;
+    const int *d_active = w.active;
+    const double *d_lpt = w.lpt;
     hipStream_t st = P.stream;
-    const auto t_host1 = std::chrono::steady_clock::now();
-    // evaluation at the start points
-    std::vector<int> hspec((size_t)n_fits), hact((size_t)n_fits), hspecp, sp1((size_t)n_fits * NW_TRY);
-    for (int i = 0; i < n_fits; ++i) hspec[i] = spec ? spec[i] : 0;
-    if (upload(d_spec1, hspec.data(), (size_t)n_fits, st) || upload(fspec.p, hspec.data(), (size_t)n_fits, st)) return -10;
-    const size_t lds_prep = hess_prep_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double), lds_fill = hess_fill_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double);
-    if (b.analytic) {
-        BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-        BDRT_HIP(hipFuncSetAttribute((const void *)newton_accept_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-        BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
-    }
     int rc;
-    if ((rc = launch_logp_grad(&P, b.x, d_spec1, n_fits, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
-    hipLaunchKernelGGL(newton_init_kernel, dim3(n_fits), dim3(256), 0, st, b, n_fits, (const double *)d_lpt, (const double *)b.gt);
-    const size_t lds_solve = newton_solve_lds_bytes(Dp);
-    BDRT_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
-    // The sequence of launches of one Levenberg-Marquardt round does not depend on what the round decides (kernels skip the
-    // fits that are done; a fit that keeps its Hessian after a rejected trial skips the probe writes and ignores the probe
-    // gradients), so several rounds are enqueued back to back and the host reads the status records once per group.
-    const char *tf_env = getenv("BDRT_NEWTON_TRIAL_FEW");      // 0: the trial points through the tile evaluator (as before round 6)
-    const bool trial_few = !(tf_env && tf_env[0] == '0');
-    const char *rp_env = getenv("BDRT_NEWTON_ROUNDS");
-    const char *trace_env = getenv("BDRT_NEWTON_TRACE");      // 1: the status records of the first eight fits at every host synchronisation, on stderr
-    const int rounds_per_sync = std::max(1, rp_env ? atoi(rp_env) : 4);
+    // probes of the fits that ask for a fresh Hessian (probe slot a = position in the active list) and their gradients
+    if (b.analytic) {
+        // (the forward quantities of this round's Hessian: left by the previous round's accept + prep kernel, by a launch of
+        //  their own in the first round)
+        if (first) hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(n_active), dim3(HP_NT), w.lds_prep, st, b, d_active, n_active);
+        hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, n_active), dim3(HP_NT), w.lds_fill, st, b, d_active, n_active);
+    } else {
+        hipLaunchKernelGGL(newton_probe_kernel, dim3(2 * D, n_active), dim3(128), 0, st, b, d_active, n_active);
+        if ((rc = launch_logp_grad(&P, b.probes, w.specp, n_active * 2 * D, 0, b.plp, b.pgrad, nullptr, nullptr, nullptr, st))) return rc;
+        hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, n_active), dim3(256), 0, st, b, d_active, n_active);
+    }
+    hipLaunchKernelGGL(newton_solve_kernel, dim3(n_active, natt), dim3(NW_NT), w.lds_solve, st, b, d_active, n_active, natt);
+    // trial points (NW_TRY step lengths per fit) as a dense batch for the evaluator, then the verdict
+    hipLaunchKernelGGL(newton_gather_kernel, dim3(n_active, NW_TRY), dim3(128), 0, st, b, d_active, n_active, b.probes, natt);
+    // (the one-workgroup-per-point evaluator where the family has one: 8 us against the tile evaluator's 24 for the eight points of
+    //  a two-start fit; the same evaluator for every batch size -- a fit's numbers do not depend on its batch)
+    rc = trial_few ? launch_logp_grad_few(&P, b.probes, w.spec1, n_active * NW_TRY, 0, w.lpt, b.gt, st, 1) : 1;
+    if (rc < 0) return rc;
+    if (rc == 1 && (rc = launch_logp_grad(&P, b.probes, w.spec1, n_active * NW_TRY, 0, w.lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
+    if (b.analytic)
+        hipLaunchKernelGGL(newton_accept_prep_kernel, dim3(n_active), dim3(HP_NT), w.lds_prep, st, b, d_active, n_active, d_lpt, (const double *)b.probes);
+    else
+        hipLaunchKernelGGL(newton_accept_kernel, dim3(n_active), dim3(256), 0, st, b, d_active, n_active, d_lpt, (const double *)b.probes);
+    return 0;
+}
+
+static void print_trace(const NewtonWork &w, long long round)
+{
+    for (int i = 0; i < (int)w.hst.size() && i < 8; ++i)
+        fprintf(stderr, "[bdrt newton trace] round %lld fit %d spec %d: lp %.12g lam %.3g |g| %.3g iters %d done %d rc %d lin %d\n", round, i, w.hspec[i],
+                w.hst[i].lp, w.hst[i].lam, w.hst[i].grad_inf, w.hst[i].iters, w.hst[i].done, w.hst[i].rc, w.hst[i].lin);
+}
+
+static int print_profile(const NewtonBufs &b)
+{
+    long long hp[NP_COUNT];
+    if (download(hp, b.prof, (size_t)NP_COUNT)) return -10;
+    const double n = hp[NP_CALLS] ? (double)hp[NP_CALLS] : 1.0;
+    fprintf(stderr, "[bdrt newton prof] D %d, %lld solve launches (workgroup 0); core cycles per launch: hessian %.0f, build %.0f, "
+            "chol diag %.0f / panel %.0f / trailing %.0f, solve %.0f, pred %.0f; wall %.1f us per launch\n", b.D, hp[NP_CALLS],
+            hp[NP_HESS] / n, hp[NP_BUILD] / n, hp[NP_DIAG] / n, hp[NP_PANEL] / n, hp[NP_TRAIL] / n, hp[NP_SOLVE] / n, hp[NP_PRED] / n,
+            hp[NP_WALL] / n / 100.0);
+    fprintf(stderr, "[bdrt newton prof] factorisations started per launch: %.2f\n", hp[NP_ATTEMPTS] / n);
+    fprintf(stderr, "[bdrt newton prof] closed-form Hessian, cycles per launch: prep");
+    for (int k = NP_PREP0; k <= NP_PREP0 + 8; ++k) fprintf(stderr, " %.0f", hp[k] / n);
+    fprintf(stderr, "; fill (row tile 8): stage %.0f, dense product %.0f, entries + stores %.0f; prep wall %.1f us\n", hp[NP_FILL0] / n, hp[NP_FILL0 + 1] / n, hp[NP_FILL0 + 2] / n, hp[NP_PREP0 + 9] / n / 100.0);
+    return 0;
+}
+
+// Newton polish of n_fits points (x0 [n_fits][D] on the host); results back to x_out, reports filled.  The host only sequences:
+// workspace and start points up, then groups of rounds between synchronisations until no fit goes on.
+int newton_polish_device(Problem &P, const double *x0, const int *spec, int n_fits, int max_iter, double tol, double *x_out, NewtonReport *rep)
+{
+    BDRT_HIP(hipSetDevice(P.device));
+    const NewtonEnv env = read_newton_env();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto t_host0 = now();
+    hipStream_t st = P.stream;
+    int rc, n_cu = 0;
+    BDRT_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P.device));
+    NewtonWork w(P.dev.D);
+    NewtonBufs &b = w.b;
+    // closed-form Hessian where the model has one, and for a Series_pos model the linear scale of the coefficients
+    const int analytic = (hess_analytic_ok(P.dev) && !env.fd) ? 1 : 0;
+    w.model(P, analytic, (analytic && P.dev.blk[0].is_pos && env.linear) ? 1 : 0);
+    if ((rc = w.alloc((size_t)n_fits, env, st)) || (rc = w.start(x0, spec, n_fits, max_iter, tol, st))) return rc;
+    const auto t_host1 = now();
+    // evaluation at the start points
+    if ((rc = w.raise_lds_limits())) return rc;
+    if ((rc = launch_logp_grad(&P, b.x, w.spec1, n_fits, 0, w.lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
+    hipLaunchKernelGGL(newton_init_kernel, dim3(n_fits), dim3(256), 0, st, b, n_fits, (const double *)w.lpt.p, (const double *)b.gt);
+    // the host reads the status records once per group of rounds
     const long long max_rounds = (long long)max_iter * 40 + 100;
-    // A host synchronisation costs ~90 us (status records down, the active list and its spectrum ids up): the lists go up only when they
-    // changed, and while some active fit is far from its stationary point (|g| > 0.01: at least three more rounds) a group is twice as long
-    std::vector<int> hact_prev;
-    int group = rounds_per_sync;
+    int group = env.rounds;
     for (long long round = 0; round < max_rounds; round += group) {
-        if (download(hst.data(), b.st, hst.size(), st)) return -10;
-        BDRT_HIP(hipStreamSynchronize(st));
-        int n_active = 0;
-        double g_far = 0.0;                                    // (the fit that will finish last decides how long the iteration runs)
-        for (int i = 0; i < n_fits; ++i) if (!hst[i].done) { hact[n_active++] = i; g_far = std::max(g_far, hst[i].grad_inf); }
-        // (small batches only: a fit that finishes inside a group keeps its rows in the evaluator's batch until the next synchronisation)
-        group = (rp_env || !(g_far > 1e-2) || n_active > 32) ? rounds_per_sync : 2 * rounds_per_sync;
-        if (trace_env && trace_env[0] == '1')
-            for (int i = 0; i < n_fits && i < 8; ++i)
-                fprintf(stderr, "[bdrt newton trace] round %lld fit %d spec %d: lp %.12g lam %.3g |g| %.3g iters %d done %d rc %d lin %d\n", round, i, hspec[i],
-                        hst[i].lp, hst[i].lam, hst[i].grad_inf, hst[i].iters, hst[i].done, hst[i].rc, hst[i].lin);
-        if (n_active == 0) break;
-        if ((int)hact_prev.size() != n_active || !std::equal(hact_prev.begin(), hact_prev.end(), hact.begin())) {
-            hact_prev.assign(hact.begin(), hact.begin() + n_active);
-            if (upload(d_active, hact.data(), (size_t)n_active, st)) return -10;
-            if (!b.analytic) hspecp.resize((size_t)n_active * 2 * D);
-            for (int a = 0; a < n_active; ++a) {
-                if (!b.analytic) std::fill(hspecp.begin() + (size_t)a * 2 * D, hspecp.begin() + (size_t)(a + 1) * 2 * D, hspec[hact[a]]);
-                for (int t = 0; t < NW_TRY; ++t) sp1[(size_t)a * NW_TRY + t] = hspec[hact[a]];
-            }
-            if ((!b.analytic && upload(d_specp, hspecp.data(), hspecp.size(), st)) || upload(d_spec1, sp1.data(), (size_t)n_active * NW_TRY, st)) return -10;
-        }
-        const int natt = b.M2 ? std::max(1, std::min(NW_ATT, n_cu / n_active)) : 1;
-        for (int r = 0; r < group; ++r) {
-            // probes of the fits that ask for a fresh Hessian (probe slot a = position in the active list) and their gradients
-            if (b.analytic) {
-                // (the forward quantities of this round's Hessian: left by the previous round's accept + prep kernel, by a launch of
-                //  their own in the first round)
-                if (round == 0 && r == 0)
-                    hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(n_active), dim3(HP_NT), lds_prep, st, b, (const int *)d_active, n_active);
-                hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, n_active), dim3(HP_NT), lds_fill, st, b, (const int *)d_active, n_active);
-            } else {
-                hipLaunchKernelGGL(newton_probe_kernel, dim3(2 * D, n_active), dim3(128), 0, st, b, (const int *)d_active, n_active);
-                if ((rc = launch_logp_grad(&P, b.probes, d_specp, n_active * 2 * D, 0, b.plp, b.pgrad, nullptr, nullptr, nullptr, st))) return rc;
-                hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, n_active), dim3(256), 0, st, b, (const int *)d_active, n_active);
-            }
-            hipLaunchKernelGGL(newton_solve_kernel, dim3(n_active, natt), dim3(NW_NT), lds_solve, st, b, (const int *)d_active, n_active, natt);
-            // trial points (NW_TRY step lengths per fit) as a dense batch for the evaluator, then the verdict
-            hipLaunchKernelGGL(newton_gather_kernel, dim3(n_active, NW_TRY), dim3(128), 0, st, b, (const int *)d_active, n_active, b.probes, natt);
-            // (the one-workgroup-per-point evaluator where the family has one: 8 us against the tile evaluator's 24 for the eight points of
-            //  a two-start fit; the same evaluator for every batch size -- a fit's numbers do not depend on its batch)
-            rc = trial_few ? launch_logp_grad_few(&P, b.probes, d_spec1, n_active * NW_TRY, 0, d_lpt, b.gt, st, 1) : 1;
-            if (rc < 0) return rc;
-            if (rc == 1 && (rc = launch_logp_grad(&P, b.probes, d_spec1, n_active * NW_TRY, 0, d_lpt, b.gt, nullptr, nullptr, nullptr, st))) return rc;
-            if (b.analytic)
-                hipLaunchKernelGGL(newton_accept_prep_kernel, dim3(n_active), dim3(HP_NT), lds_prep, st, b, (const int *)d_active, n_active,
-                                   (const double *)d_lpt, (const double *)b.probes);
-            else
-                hipLaunchKernelGGL(newton_accept_kernel, dim3(n_active), dim3(256), 0, st, b, (const int *)d_active, n_active, (const double *)d_lpt,
-                                   (const double *)b.probes);
-        }
+        if ((rc = w.sync_active(st))) return rc;
+        group = group_length(env, w.g_far, w.n_active);
+        if (env.trace) print_trace(w, round);
+        if (w.n_active == 0) break;
+        const int natt = b.M2 ? std::max(1, std::min(NW_ATT, n_cu / w.n_active)) : 1;
+        for (int r = 0; r < group; ++r)
+            if ((rc = enqueue_round(P, w, env.trial_few, natt, round == 0 && r == 0))) return rc;
         BDRT_HIP(hipGetLastError());
     }
-    if (download(hst.data(), b.st, hst.size(), st) || download(x_out, b.x, nD, st)) return -10;
+    if (download(w.hst.data(), b.st, w.hst.size(), st) || download(x_out, b.x, (size_t)n_fits * b.D, st)) return -10;
     BDRT_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < n_fits; ++i) {
-        if (lp_out) lp_out[i] = hst[i].lp;
-        if (ginf_out) ginf_out[i] = hst[i].grad_inf;
-        if (iters_out) iters_out[i] = hst[i].iters;
-        if (rc_out) rc_out[i] = hst[i].done ? hst[i].rc : 1;
-        if (n_evals_out) n_evals_out[i] = hst[i].n_evals;
+        const NewtonState &h = w.hst[i];
+        rep[i] = NewtonReport{h.lp, h.grad_inf, h.iters, h.done ? h.rc : 1, h.n_evals};
     }
-    if (b.prof) {
-        long long hp[NP_COUNT];
-        if (download(hp, b.prof, (size_t)NP_COUNT)) return -10;
-        const double n = hp[NP_CALLS] ? (double)hp[NP_CALLS] : 1.0;
-        fprintf(stderr, "[bdrt newton prof] D %d, %lld solve launches (workgroup 0); core cycles per launch: hessian %.0f, build %.0f, "
-                "chol diag %.0f / panel %.0f / trailing %.0f, solve %.0f, pred %.0f; wall %.1f us per launch\n", D, hp[NP_CALLS],
-                hp[NP_HESS] / n, hp[NP_BUILD] / n, hp[NP_DIAG] / n, hp[NP_PANEL] / n, hp[NP_TRAIL] / n, hp[NP_SOLVE] / n, hp[NP_PRED] / n,
-                hp[NP_WALL] / n / 100.0);
-        fprintf(stderr, "[bdrt newton prof] factorisations started per launch: %.2f\n", hp[NP_ATTEMPTS] / n);
-        fprintf(stderr, "[bdrt newton prof] closed-form Hessian, cycles per launch: prep");
-        for (int k = NP_PREP0; k <= NP_PREP0 + 8; ++k) fprintf(stderr, " %.0f", hp[k] / n);
-        fprintf(stderr, "; fill (row tile 8): stage %.0f, dense product %.0f, entries + stores %.0f; prep wall %.1f us\n", hp[NP_FILL0] / n, hp[NP_FILL0 + 1] / n, hp[NP_FILL0 + 2] / n, hp[NP_PREP0 + 9] / n / 100.0);
-    }
-    const auto t_host2 = std::chrono::steady_clock::now();
-    // (what the profile times as "frees": the matrices and vectors go here and not at the closing brace)
-    for (DevBuf<double> *d : {&M2, &H, &M, &s, &xt, &gt, &probes, &pgrad, &hws, &x, &g, &hstep, &plp, &lpt}) d->reset();
-    if (prof_env && prof_env[0] == '1') {
-        const auto t_host3 = std::chrono::steady_clock::now();
+    if (b.prof && (rc = print_profile(b))) return rc;
+    const auto t_host2 = now();
+    w.release_arrays();
+    if (env.prof) {
         auto us = [](auto a, auto b) { return (double)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
         fprintf(stderr, "[bdrt newton prof] host: allocations + uploads %.0f us, iteration %.0f us, frees %.0f us\n", us(t_host0, t_host1), us(t_host1, t_host2),
-                us(t_host2, t_host3));
+                us(t_host2, now()));
     }
     return 0;
 }
 
-// the closed-form Hessian at ONE point (tests): H_out [D][D] row-major on the host; 1 when the problem has no closed form here.
-// lin: the coefficients on the linear scale, as the iteration takes them once its damping has dropped (lam stays 0 here, so the
-// kernels' own rule selects the branch from lin_ok); 1 as well when that is asked of a model whose coefficients are free.
-// held_out [D] (optional): the workspace's `act` slots, 1.0 for a coefficient held at its floor.
-int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double *H_out, double *held_out)
+// the state of a fit as the debug entry's caller holds it (bdrt_newton_state) <-> as the kernels do: the members both have
+template <class From, class To> static void copy_state(const From &a, To &b)
 {
+    b.lp = a.lp; b.lam = a.lam; b.pred = a.pred; b.gs = a.gs; b.ss = a.ss; b.grad_inf = a.grad_inf; b.tol = a.tol; b.lp_trial = a.lp_trial;
+    b.iters = a.iters; b.max_iter = a.max_iter; b.lin = a.lin; b.rc = a.rc; b.done = a.done; b.need_hess = a.need_hess; b.n_evals = a.n_evals;
+}
+
+}  // namespace bdrt
+
+using namespace bdrt;
+
+extern "C" {
+
+// closed-form Hessian of the log-posterior (no Jacobian) at ONE unconstrained point, as the Newton iteration uses it (tests):
+// H_out [D x D] row-major on the host; returns 1 when the model has no closed form here (the iteration then differences gradients).
+// lin = 1: with the coefficients of a Series_pos model on the linear scale, as the iteration takes them once its damping has dropped
+// (lam stays 0 here, so the kernels' own rule selects the branch from lin_ok); 1 as well when that is asked of a model without
+// <lower=0> coefficients.  held_out [D] (may be null): the workspace's `act` slots, 1.0 for a coefficient held at its floor.
+int bdrt_debug_hessian_lin(bdrt_problem *p, const double *theta, int spec, int lin, double *H_out, double *held_out)
+{
+    if (!p || !theta || !H_out || spec < 0 || spec >= p->impl.dev.n_spectra || lin < 0 || lin > 1) { set_error("bdrt_debug_hessian_lin: bad arguments"); return -1; }
+    Problem &P = p->impl;
     if (!hess_analytic_ok(P.dev)) return 1;
     if (lin && !P.dev.blk[0].is_pos) return 1;
-    const int D = P.dev.D, Dp = (D + 15) & ~15;
     BDRT_HIP(hipSetDevice(P.device));
-    NewtonBufs b;
-    memset(&b, 0, sizeof(b));
-    b.D = D; b.Dp = Dp; b.analytic = 1; b.dP = (const DevProblem *)P.d_dev;
-    b.lin_ok = lin ? 1 : 0;
-    const HessLayout hlay(P.dev.nf, P.dev.blk[0].K);
-    DevBuf<double> x, g, H, M, hws, d_lp;
-    DevBuf<NewtonState> dst;
-    DevBuf<int> d_act, d_spec;
-    BDRT_HIP(x.alloc((size_t)D)); BDRT_HIP(g.alloc((size_t)D));
-    BDRT_HIP(H.alloc((size_t)Dp * Dp)); BDRT_HIP(M.alloc((size_t)Dp * Dp));
-    BDRT_HIP(hws.alloc((size_t)hlay.total)); BDRT_HIP(dst.alloc(1));
-    BDRT_HIP(d_act.alloc(1)); BDRT_HIP(d_spec.alloc(1)); BDRT_HIP(d_lp.alloc(1));
-    b.x = x; b.g = g; b.H = H; b.M = M; b.hws = hws; b.st = dst; b.fspec = d_spec;
-    NewtonState hs;
-    memset(&hs, 0, sizeof(hs)); hs.need_hess = 1; hs.lam = 0.0;
+    NewtonWork w(P.dev.D);
+    const NewtonBufs &b = w.b;
+    const int D = b.D, Dp = b.Dp;
+    w.model(P, 1, lin);
+    BDRT_HIP(w.x.alloc((size_t)D)); BDRT_HIP(w.g.alloc((size_t)D)); BDRT_HIP(w.H.alloc((size_t)Dp * Dp)); BDRT_HIP(w.M.alloc((size_t)Dp * Dp));
+    BDRT_HIP(w.hws.alloc((size_t)b.hl_total)); BDRT_HIP(w.state.alloc(1)); BDRT_HIP(w.active.alloc(1)); BDRT_HIP(w.fspec.alloc(1)); BDRT_HIP(w.lpt.alloc(1));
+    w.bind();
+    NewtonState hs{};
+    hs.need_hess = 1; hs.lam = 0.0;
     const int zero = 0;
     hipStream_t st = P.stream;
-    if (upload(b.st, &hs, 1, st) || upload(b.x, theta, (size_t)D, st) || upload(d_act.p, &zero, 1, st) || upload(d_spec.p, &spec, 1, st)) return -10;
-    if (int rc = launch_logp_grad(&P, b.x, d_spec, 1, 0, d_lp, b.g, nullptr, nullptr, nullptr, st)) return rc;
-    const size_t lds_prep = hess_prep_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double), lds_fill = hess_fill_lds_doubles(P.dev.nf, P.dev.blk[0].K) * sizeof(double);
-    BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-    BDRT_HIP(hipFuncSetAttribute((const void *)newton_hess_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
-    hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(1), dim3(HP_NT), lds_prep, st, b, (const int *)d_act.p, 1);
-    hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, 1), dim3(HP_NT), lds_fill, st, b, (const int *)d_act.p, 1);
+    if (upload(b.st, &hs, 1, st) || upload(b.x, theta, (size_t)D, st) || upload(w.active.p, &zero, 1, st) || upload(w.fspec.p, &spec, 1, st)) return -10;
+    if (int rc = launch_logp_grad(&P, b.x, w.fspec, 1, 0, w.lpt, b.g, nullptr, nullptr, nullptr, st)) return rc;
+    if (int rc = w.raise_lds_limits()) return rc;
+    hipLaunchKernelGGL(newton_hess_prep_kernel, dim3(1), dim3(HP_NT), w.lds_prep, st, b, (const int *)w.active.p, 1);
+    hipLaunchKernelGGL(newton_hess_fill_kernel, dim3(Dp / 16, 1), dim3(HP_NT), w.lds_fill, st, b, (const int *)w.active.p, 1);
     BDRT_HIP(hipGetLastError());
     std::vector<double> hh((size_t)Dp * Dp);
-    if (download(hh.data(), b.H, hh.size(), st) || (held_out && download(held_out, b.hws + hlay.act, (size_t)D, st))) return -10;
+    if (download(hh.data(), b.H, hh.size(), st) || (held_out && download(held_out, b.hws + b.hl_act, (size_t)D, st))) return -10;
     BDRT_HIP(hipStreamSynchronize(st));
     // (the kernels write the block lower triangle: mirror it)
     for (int i = 0; i < D; ++i)
@@ -904,104 +983,78 @@ int hessian_at_point(Problem &P, const double *theta, int spec, int lin, double 
     return 0;
 }
 
-// the debug entries' stand-in for the closed-form Hessian's workspace: the three fields the solve, gather and accept kernels read --
-// tz [D], act [D], the floor -- and the layout offsets that point at them (tz == nullptr: the log scale, no workspace)
-static int debug_lin_workspace(NewtonBufs &b, DevBuf<double> &hws, int D, const double *tz, const double *held, double floor_x, int o_x, int Kx)
-{
-    if (!tz) return 0;
-    std::vector<double> w((size_t)2 * D + 1);
-    for (int i = 0; i < D; ++i) { w[i] = tz[i]; w[(size_t)D + i] = held && held[i] != 0.0 ? 1.0 : 0.0; }
-    w[(size_t)2 * D] = floor_x;
-    if (int rc = upload(hws, w.data(), w.size())) return rc;
-    b.analytic = 1; b.lin_ok = 1; b.hws = hws;
-    b.hl_total = 2 * D + 1; b.hl_tz = 0; b.hl_act = D; b.hl_floor = 2 * D; b.o_x = o_x; b.Kx = Kx;
-    return 0;
-}
+int bdrt_debug_hessian(bdrt_problem *p, const double *theta, int spec, double *H_out) { return bdrt_debug_hessian_lin(p, theta, spec, 0, H_out, nullptr); }
 
-// One launch of the damped solve on supplied data (tests): newton_build_kernel's need_hess == 0 branch, newton_solve_kernel with
+// One launch of the damped solve on the caller's data (tests): newton_build_kernel's need_hess == 0 branch, newton_solve_kernel with
 // natt attempts, newton_gather_kernel -- the launches of a round of newton_polish_device for one fit that keeps its Hessian.
-int newton_solve_at(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz, const double *held,
-                    double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out, bdrt_newton_solve_record *rec)
+int bdrt_debug_newton_solve(const double *H, const double *g, const double *x, int D, double lam, int natt, const double *tz,
+                            const double *held, double floor_x, int o_x, int Kx, double *L_out, double *s_out, double *trial_out,
+                            bdrt_newton_solve_record *rec)
 {
-    const int Dp = (D + 15) & ~15;
-    const size_t lds_solve = newton_solve_lds_bytes(Dp), nM = (size_t)Dp * Dp;
-    if (lds_solve + 64 > 160 * 1024) { set_error("bdrt_debug_newton_solve: D = %d needs %zu bytes of LDS", D, lds_solve); return -2; }     // (+ the kernel's static LDS)
+    if (!H || !g || !x || !L_out || !s_out || !trial_out || !rec || D < 1 || natt < 1 || natt > 6 || !(lam > 0.0) ||
+        (tz && (o_x < 0 || Kx < 0 || o_x + Kx > D))) { set_error("bdrt_debug_newton_solve: bad arguments"); return -1; }
+    NewtonWork w(D);
+    const NewtonBufs &b = w.b;
+    const int Dp = b.Dp;
+    const size_t nM = (size_t)Dp * Dp;
+    if (w.lds_solve + 64 > 160 * 1024) { set_error("bdrt_debug_newton_solve: D = %d needs %zu bytes of LDS", D, w.lds_solve); return -2; }     // (+ the kernel's static LDS)
     bind_process_device();
-    NewtonBufs b;
-    memset(&b, 0, sizeof(b));
-    b.D = D; b.Dp = Dp;
-    DevBuf<double> dx, dg, ds, dxt, dH, dM, dM2, hws, dtrial;
-    DevBuf<NewtonAttempt> datt;
-    DevBuf<NewtonState> dst;
-    DevBuf<int> d_act;
     std::vector<double> hh(nM, 0.0);
     for (int i = 0; i < D; ++i) memcpy(&hh[(size_t)i * Dp], H + (size_t)i * D, (size_t)D * sizeof(double));
-    NewtonState hs;
-    memset(&hs, 0, sizeof(hs));
+    NewtonState hs{};
     hs.lam = lam; hs.rc = 1; hs.lin = tz ? 1 : 0;
-    const int zero = 0;
     int rc;
-    if ((rc = upload(dx, x, (size_t)D)) || (rc = upload(dg, g, (size_t)D)) || (rc = upload(dH, hh.data(), nM)) || (rc = upload(dst, &hs, 1)) ||
-        (rc = upload(d_act, &zero, 1)) || (rc = debug_lin_workspace(b, hws, D, tz, held, floor_x, o_x, Kx))) return rc;
-    BDRT_HIP(ds.alloc((size_t)NW_ATT * D)); BDRT_HIP(dxt.alloc((size_t)NW_ATT * D)); BDRT_HIP(dtrial.alloc((size_t)NW_TRY * D));
-    BDRT_HIP(dM.alloc(nM)); BDRT_HIP(datt.alloc(NW_ATT));
-    BDRT_HIP(hipMemset(datt, 0, NW_ATT * sizeof(NewtonAttempt)));
+    if ((rc = w.one_fit(x, g, hs, tz, held, floor_x, o_x, Kx)) || (rc = upload(w.H, hh.data(), nM))) return rc;
+    BDRT_HIP(w.s.alloc((size_t)NW_ATT * D)); BDRT_HIP(w.xt.alloc((size_t)NW_ATT * D)); BDRT_HIP(w.probes.alloc((size_t)NW_TRY * D)); BDRT_HIP(w.M.alloc(nM));
+    BDRT_HIP(w.att.alloc(NW_ATT));
+    BDRT_HIP(hipMemset(w.att, 0, NW_ATT * sizeof(NewtonAttempt)));
     if (natt > 1) {
         // (the speculative attempts write the lower block triangle of their matrices only: the rest reads as zero)
-        BDRT_HIP(dM2.alloc((NW_ATT - 1) * nM));
-        BDRT_HIP(hipMemset(dM2, 0, (NW_ATT - 1) * nM * sizeof(double)));
+        BDRT_HIP(w.M2.alloc((NW_ATT - 1) * nM));
+        BDRT_HIP(hipMemset(w.M2, 0, (NW_ATT - 1) * nM * sizeof(double)));
     }
-    b.x = dx; b.g = dg; b.s = ds; b.xt = dxt; b.H = dH; b.M = dM; b.M2 = dM2; b.att = datt; b.st = dst;
-    BDRT_HIP(hipFuncSetAttribute((const void *)newton_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
+    w.bind();
+    if ((rc = w.raise_lds_limits())) return rc;
     hipStream_t st = nullptr;
-    hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, 1), dim3(256), 0, st, b, (const int *)d_act.p, 1);
-    hipLaunchKernelGGL(newton_solve_kernel, dim3(1, natt), dim3(NW_NT), lds_solve, st, b, (const int *)d_act.p, 1, natt);
-    hipLaunchKernelGGL(newton_gather_kernel, dim3(1, NW_TRY), dim3(128), 0, st, b, (const int *)d_act.p, 1, dtrial.p, natt);
+    hipLaunchKernelGGL(newton_build_kernel, dim3(Dp / 16, 1), dim3(256), 0, st, b, (const int *)w.active.p, 1);
+    hipLaunchKernelGGL(newton_solve_kernel, dim3(1, natt), dim3(NW_NT), w.lds_solve, st, b, (const int *)w.active.p, 1, natt);
+    hipLaunchKernelGGL(newton_gather_kernel, dim3(1, NW_TRY), dim3(128), 0, st, b, (const int *)w.active.p, 1, b.probes, natt);
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipStreamSynchronize(st));
     NewtonAttempt hatt[NW_ATT];
-    if (download(hatt, (const NewtonAttempt *)datt.p, (size_t)NW_ATT) || download(&hs, (const NewtonState *)dst.p, 1)) return -10;
+    if (download(hatt, (const NewtonAttempt *)b.att, (size_t)NW_ATT) || download(&hs, (const NewtonState *)b.st, 1)) return -10;
     int c = 0;
     while (c + 1 < natt && !hatt[c].ok) ++c;                           // the gather kernel's choice
-    const double *Mc = c ? dM2.p + (size_t)(c - 1) * nM : dM.p;
-    if (download(L_out, Mc, nM) || download(s_out, (const double *)ds.p + (size_t)c * D, (size_t)D) ||
-        download(trial_out, (const double *)dtrial.p, (size_t)NW_TRY * D)) return -10;
+    const double *Mc = c ? b.M2 + (size_t)(c - 1) * nM : b.M;
+    if (download(L_out, Mc, nM) || download(s_out, (const double *)b.s + (size_t)c * D, (size_t)D) ||
+        download(trial_out, (const double *)b.probes, (size_t)NW_TRY * D)) return -10;
     rec->ok = hatt[c].ok; rec->attempt = c; rec->rc = hs.rc; rec->done = hs.done;
     rec->lam = hs.lam; rec->pred = hs.pred; rec->gs = hs.gs; rec->ss = hs.ss;
     return 0;
 }
 
-// One launch of newton_accept_kernel on supplied data (tests): the state, the point and its gradient before and after
-int newton_accept_at(bdrt_newton_state *s, double *x, double *g, int D, const double *trial, const double *lp_t, const double *gt,
-                     const double *tz, const double *held, double floor_x, int o_x, int Kx)
+// One launch of newton_accept_kernel on the caller's data (tests): the state, the point and its gradient before and after
+int bdrt_debug_newton_accept(bdrt_newton_state *s, double *x, double *g, int D, const double *trial, const double *lp_t,
+                             const double *gt, const double *tz, const double *held, double floor_x, int o_x, int Kx)
 {
+    if (!s || !x || !g || !trial || !lp_t || !gt || D < 1 || (tz && (o_x < 0 || Kx < 0 || o_x + Kx > D))) { set_error("bdrt_debug_newton_accept: bad arguments"); return -1; }
     bind_process_device();
-    NewtonBufs b;
-    memset(&b, 0, sizeof(b));
-    b.D = D; b.Dp = (D + 15) & ~15;
-    DevBuf<double> dx, dg, dgt, dtrial, dlp, hws;
-    DevBuf<NewtonState> dst;
-    DevBuf<int> d_act;
-    NewtonState hs;
-    memset(&hs, 0, sizeof(hs));
-    hs.lp = s->lp; hs.lam = s->lam; hs.pred = s->pred; hs.gs = s->gs; hs.ss = s->ss; hs.grad_inf = s->grad_inf; hs.tol = s->tol;
-    hs.lp_trial = s->lp_trial; hs.iters = s->iters; hs.max_iter = s->max_iter; hs.lin = tz ? s->lin : 0; hs.rc = s->rc; hs.done = s->done;
-    hs.need_hess = s->need_hess; hs.n_evals = s->n_evals;
-    const int zero = 0;
+    NewtonWork w(D);
+    const NewtonBufs &b = w.b;
+    NewtonState hs{};
+    copy_state(*s, hs);
+    if (!tz) hs.lin = 0;
     int rc;
-    if ((rc = upload(dx, (const double *)x, (size_t)D)) || (rc = upload(dg, (const double *)g, (size_t)D)) ||
-        (rc = upload(dgt, gt, (size_t)NW_TRY * D)) || (rc = upload(dtrial, trial, (size_t)NW_TRY * D)) || (rc = upload(dlp, lp_t, (size_t)NW_TRY)) ||
-        (rc = upload(dst, &hs, 1)) || (rc = upload(d_act, &zero, 1)) || (rc = debug_lin_workspace(b, hws, D, tz, held, floor_x, o_x, Kx))) return rc;
-    b.x = dx; b.g = dg; b.gt = dgt; b.st = dst;
+    if ((rc = w.one_fit(x, g, hs, tz, held, floor_x, o_x, Kx)) || (rc = upload(w.gt, gt, (size_t)NW_TRY * D)) ||
+        (rc = upload(w.probes, trial, (size_t)NW_TRY * D)) || (rc = upload(w.lpt, lp_t, (size_t)NW_TRY))) return rc;
+    w.bind();
     hipStream_t st = nullptr;
-    hipLaunchKernelGGL(newton_accept_kernel, dim3(1), dim3(256), 0, st, b, (const int *)d_act.p, 1, (const double *)dlp.p, (const double *)dtrial.p);
+    hipLaunchKernelGGL(newton_accept_kernel, dim3(1), dim3(256), 0, st, b, (const int *)w.active.p, 1, (const double *)w.lpt.p, (const double *)b.probes);
     BDRT_HIP(hipGetLastError());
     BDRT_HIP(hipStreamSynchronize(st));
-    if (download(&hs, (const NewtonState *)dst.p, 1) || download(x, (const double *)dx.p, (size_t)D) || download(g, (const double *)dg.p, (size_t)D)) return -10;
-    s->lp = hs.lp; s->lam = hs.lam; s->pred = hs.pred; s->gs = hs.gs; s->ss = hs.ss; s->grad_inf = hs.grad_inf; s->tol = hs.tol;
-    s->lp_trial = hs.lp_trial; s->iters = hs.iters; s->max_iter = hs.max_iter; s->lin = hs.lin; s->rc = hs.rc; s->done = hs.done;
-    s->need_hess = hs.need_hess; s->n_evals = hs.n_evals;
+    if (download(&hs, (const NewtonState *)b.st, 1) || download(x, (const double *)b.x, (size_t)D) || download(g, (const double *)b.g, (size_t)D)) return -10;
+    copy_state(hs, *s);
     return 0;
 }
 
-}  // namespace bdrt
+}  // extern "C"

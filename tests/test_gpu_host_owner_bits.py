@@ -30,15 +30,15 @@ QP_NVEC = 14                                     # bdrt_qp.hip
 LDS_LIMIT = (160 * 1024 - 2560) // 8             # doubles: what bdrt_qp_box_batch / bdrt_ridge_ex may take of the LDS
 
 
-def _check(case, outs):
+def _check(case, outs, fixture=FIXTURE, record=RECORD):
     """outs: {name: array} of one case, compared with (or recorded as) the fixture's '<case>/<name>'"""
     outs = {'%s/%s' % (case, k): np.asarray(v) for k, v in outs.items()}
-    if RECORD:
-        table = dict(np.load(RECORD)) if os.path.exists(RECORD) else {}
+    if record:
+        table = dict(np.load(record)) if os.path.exists(record) else {}
         table.update(outs)
-        np.savez_compressed(RECORD, **table)
+        np.savez_compressed(record, **table)
         return
-    want = np.load(FIXTURE)
+    want = np.load(fixture)
     wrong = []
     for k, got in outs.items():
         ref = want[k]
